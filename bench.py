@@ -19,14 +19,22 @@ own subtrees on their GPU, then the top supernodes with their large GEMMs split 
 summed once over RCCL, block by block (sharded.py, mode "distributed").  --scale weak (default): the matrix rows per GPU
 stay those of config 2 (n = N x 128^3: g = round(128 N^(1/3)) = 161, 203, 256 -- N = 8 IS BASELINE config 4, 256^3 over
 8 GPUs); --scale weak-flops: the flops per GPU stay those of 128^3 (g = round(128 N^(1/6)): 144, 161, 181; also timed as
-`secondary.weak_flops` in the default N > 1 run); --scale strong: the same 128^3 matrix on every N.  An explicit --grid is
+`secondary.weak_flops` in an N > 1 run with --full); --scale strong: the same 128^3 matrix on every N.  An explicit --grid is
 used as given, whatever --scale says.  --mp subtree-replicated: top supernodes replicated, one all-reduce.
 --mp replicas: one independent matrix per GPU (the reference's multi-matrix mode, SparseFrame.c:3375).
 
-The JSON line also carries
+A plain run sets up, warms up, times the --steps steps and prints the headline line.  With --full the JSON line also carries
   roofline     : the Schur-update kernel (k_gemm<1>: fp64 MFMA GEMM + fused mapped scatter), executed
                  update flops / its summed launch time (HIP events on the plan's stream)
-  cpu_baseline : the CPU oracle (a port of the reference's CPU path on OpenBLAS) on a bounded sample.
+  cpu_baseline : the CPU oracle (a port of the reference's CPU path on OpenBLAS) on a bounded sample
+and the device validate (config.residual_*), the host-buffer boundary (config.pcie_inclusive) and the other BASELINE
+configs (secondary); --no-roofline / --no-pcie / --no-secondary / --cpu-grid trim what --full adds.
+
+--dump-outputs DIR: after the timed steps, the factor of the last step (what get_factor() would hand a caller, reference
+layout) as DIR/factor_sample.npy (float64): the whole factor when it holds at most DUMP_BLOCKS x DUMP_BLOCK entries,
+otherwise DUMP_BLOCKS blocks of DUMP_BLOCK consecutive entries at seeded random block-aligned places, whose first indices
+are DIR/factor_sample_offsets.npy (float64, exact).  The inputs are generated deterministically, so two builds run with the
+same arguments can be compared output for output.
 """
 import argparse
 import importlib
@@ -43,6 +51,40 @@ FP64_MFMA_PEAK_TFLOPS = 78.6   # MI355X datasheet fp64 matrix; v_mfma_f64_16x16x
 
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E peak (guide: 8 TB/s spec, ~6.3 TB/s achievable)
+
+DUMP_BLOCK = 1024              # --dump-outputs: consecutive factor entries per sampled block
+DUMP_BLOCKS = 4096             # blocks per sample: 32 MiB of float64 (+ 32 KiB of offsets)
+DUMP_SEED = 20240611
+
+
+def dump_factor(out_dir, xsize, read):
+    """--dump-outputs: the factor (xsize doubles, reference layout) or a seeded block sample of it; read(b, e) returns
+    entries [b, e) as float64"""
+    import numpy as np
+    nblk = xsize // DUMP_BLOCK
+    if nblk <= DUMP_BLOCKS:
+        starts = np.zeros(1, dtype=np.int64)
+        sample = read(0, xsize)
+    else:
+        starts = np.sort(np.random.default_rng(DUMP_SEED).choice(nblk, DUMP_BLOCKS, replace=False)).astype(np.int64) * DUMP_BLOCK
+        sample = np.concatenate([read(int(b), int(b) + DUMP_BLOCK) for b in starts])
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "factor_sample.npy"), np.ascontiguousarray(sample, dtype=np.float64))
+    np.save(os.path.join(out_dir, "factor_sample_offsets.npy"), starts.astype(np.float64))
+
+
+def plan_factor_range(sf, plan):
+    """read(b, e) over a whole plan's device factor (sf_chol_plan_get_factor_range: bounds-checked D2H, LU packed on the device)"""
+    import ctypes as C
+    import numpy as np
+
+    def read(b, e):
+        buf = np.empty(max(e - b, 1), dtype=np.float64)
+        rc = sf.lib.sf_chol_plan_get_factor_range(plan._h, C.c_int64(b), C.c_int64(e), buf.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != 0:
+            raise RuntimeError(f"sf_chol_plan_get_factor_range({b}, {e}) failed: {rc}")
+        return buf[:e - b]
+    return read
 
 
 def config1_case(sf, np):
@@ -331,7 +373,15 @@ def main():
                     help="N = 1: skip the host-buffer boundary lines (values H2D + factorize + overlapped factor D2H at plan level and "
                          "through the struct entry point SparseFrame_factorize), reported in config.pcie_inclusive; never `value`")
     ap.add_argument("--pcie", action="store_true", help="(default now; kept for compatibility)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: roofline, device validate and residuals, "
+                         "pcie_inclusive, the secondary configs, the CPU baseline (N > 1: the distributed solve and the weak-flops "
+                         "case); off by default, the --no-* options and --cpu-grid trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's factor (or a seeded sample of it) as .npy files into DIR")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     ngpu = max(args.gpus, 1)
     if ngpu > 1 and "WORLD_SIZE" not in os.environ:
@@ -480,6 +530,17 @@ def main():
             dist.destroy_process_group()
         raise SystemExit(3)
 
+    if args.dump_outputs:
+        # the factor of the last timed step, before anything below factorizes again; a sharded factor is gathered first
+        # (every rank takes part), as --check does
+        if sharded is not None:
+            Lsx = sharded.gather_factor()
+            if rank == 0:
+                dump_factor(args.dump_outputs, int(sym.xsize), lambda b, e: Lsx[b:e])
+            del Lsx
+        elif rank == 0:
+            dump_factor(args.dump_outputs, int(sym.xsize), plan_factor_range(sf, plan))
+
     out = {
         "metric": "numeric-factorization GFLOP/s (supernodal %s)" % ("LU, pivoting inside the diagonal blocks" if lu else "Cholesky"),
         "value": round(value, 2), "unit": "GFLOP/s", "n_gpus": ngpu, "ranks_seen": ranks_seen, "collectives": collectives,
@@ -518,7 +579,7 @@ def main():
                                    "the matrix values (8 B x nnz_input) and the factor's D2H are excluded -- see pcie_inclusive"},
     }
 
-    if rank == 0 and not args.no_roofline and sharded is None:
+    if args.full and rank == 0 and not args.no_roofline and sharded is None:
         plan.set_profiling(True)
         plan.factorize(sync=True)
         plan.set_profiling(False)
@@ -562,7 +623,7 @@ def main():
             hb["schur_gemm_mfma"] = out["roofline"]
             out["roofline"] = hb
 
-    if sharded is not None and sharded.mode == "distributed" and getattr(sharded.engine, "comm", None) is not None:
+    if args.full and sharded is not None and sharded.mode == "distributed" and getattr(sharded.engine, "comm", None) is not None:
         # correctness of the multi-GPU run, outside the timed region: the distributed solve with the factor left on the ranks
         # (every rank takes part), then the reference's validate() residual on rank 0 (numpy over the analysed matrix)
         try:
@@ -590,7 +651,7 @@ def main():
             if rank == 0:
                 out["config"]["residual_distributed_solve"] = f"failed: {e}"
 
-    if rank == 0 and sharded is None:
+    if args.full and rank == 0 and sharded is None:
         # the reference's validate() with nothing leaving the device but the scalar: solve with the resident factor and
         # residual kernels over the plan's copy of A (sf_chol_plan_validate); the numpy form of the same residual is the
         # host cross-check (Cholesky).  No oracle code and no 30 GB download involved.
@@ -600,7 +661,7 @@ def main():
             out["config"]["residual_host_check"] = sf.validate_solution(sym, xs)
         out["config"]["device_solve_ms"] = round(plan.stat("last_solve_ms"), 3)
 
-    if rank == 0 and sharded is None and not args.no_pcie:
+    if args.full and rank == 0 and sharded is None and not args.no_pcie:
         try:
             # Host-buffer boundary (never `value`): what the drop-in entry point costs.
             #  (a) plan level: values H2D + factorize + factor D2H into pageable memory, the download of finished blocks
@@ -677,7 +738,7 @@ def main():
         out["config"]["residual"] = res
         del Lsx
 
-    if rank == 0 and ngpu == 1 and not args.no_secondary and not lu and args.workload == "lap3d" and args.grid in (0, 128):
+    if args.full and rank == 0 and ngpu == 1 and not args.no_secondary and not lu and args.workload == "lap3d" and args.grid in (0, 128):
         def guarded(fn, *a, **kw):
             # a secondary case that fails must not take the headline with it: its entry says what happened
             try:
@@ -695,7 +756,7 @@ def main():
 
     if args.cpu_grid < 0:
         args.cpu_grid = min(N, 128)
-    if rank == 0 and ngpu == 1 and args.cpu_grid > 0:
+    if args.full and rank == 0 and ngpu == 1 and args.cpu_grid > 0:
         import oracle
         threads = args.cpu_threads or min(os.cpu_count() or 1, 16)   # reference: min(omp_max, 16), SparseFrame.c:3357
         binfo = oracle.blas_init("auto", threads=threads)
@@ -729,7 +790,7 @@ def main():
     elif plan is not None:
         plan.close()
 
-    if (shard_one and world > 1 and not args.no_secondary and not lu and args.workload == "lap3d" and args.mp == "subtree"
+    if (args.full and shard_one and world > 1 and not args.no_secondary and not lu and args.workload == "lap3d" and args.mp == "subtree"
             and args.scale == "weak"):
         # the other weak-scaling rule (flops per GPU fixed: 144 / 161 / 181 for N = 2 / 4 / 8), timed after the headline case with a
         # few steps; every rank takes part.  A failure here is reported inside the object and never costs the headline line.

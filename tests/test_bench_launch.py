@@ -61,7 +61,7 @@ def test_no_launcher_starts_the_ranks_itself_and_never_prints_a_one_rank_value()
 @pytest.mark.parametrize("mp", ["subtree", "replicas"])
 def test_gpus_2_without_launcher_runs_two_ranks(mp):
     p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--grid", "24", "--cpu-grid", "0",
-                        "--mp", mp],
+                        "--mp", mp, "--full"],
                        env=_clean_env(SF_BENCH_BACKEND="gloo", SF_BENCH_DEVICE="0"), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
@@ -94,3 +94,82 @@ def test_ranks_seen_mismatch_gives_no_value():
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 3, (p.returncode, p.stderr[-3000:])
     assert "counted 0 ranks" in p.stderr and not _json_lines(p.stdout)
+
+
+def test_steps_must_be_at_least_one():
+    """--steps is the number of timed steps: 0 would time nothing and is refused before anything runs"""
+    p = subprocess.run([sys.executable, BENCH, "--steps", "0"], env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=300, cwd=ROOT)
+    assert p.returncode != 0 and "--steps" in p.stderr, p.stderr[-2000:]
+    assert not _json_lines(p.stdout), p.stdout[-2000:]
+
+
+def _bench_line(*args):
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", *args], env=_clean_env(), stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
+    lines = _json_lines(p.stdout)
+    assert len(lines) == 1, p.stdout[-3000:]
+    return lines[0]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_full_adds_the_rest():
+    """a plain run times --steps steps and prints the headline only; --full adds roofline, device validate, the host-buffer
+    boundary and the CPU baseline"""
+    plain = _bench_line("--steps", "3", "--warmup", "1", "--grid", "16")
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["value"] > 0 and plain["ms_per_step"] > 0, plain
+    assert plain["unit"] == "GFLOP/s" and plain["higher_is_better"] is True and plain["dtype"] == "f64", plain
+    assert not {"roofline", "cpu_baseline", "secondary"} & set(plain), plain
+    assert not {"residual_device_solve", "residual_host_check", "pcie_inclusive"} & set(plain["config"]), plain["config"]
+    full = _bench_line("--steps", "2", "--warmup", "1", "--grid", "16", "--full")
+    assert full["steps"] == 2 and full["value"] > 0
+    assert full["roofline"]["kernel_ms"] >= 0 and full["cpu_baseline"]["info"] == 0, full
+    assert full["config"]["residual_device_solve"] <= 1e-13 and full["config"]["residual_host_check"] <= 1e-13, full["config"]
+    assert "plan_second_call_ms" in full["config"]["pcie_inclusive"], full["config"]["pcie_inclusive"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("grid,method", [(16, "cholesky"), (40, "cholesky"), (12, "lu")])
+def test_dump_outputs_is_the_factor_of_the_timed_steps(tmp_path, grid, method):
+    """--dump-outputs writes the factor the timed steps left on the device (whole, or seeded blocks of it when it is larger
+    than the sample), equal to the same factorization run in this process"""
+    import numpy as np
+    from util import sf
+    out = tmp_path / "outputs"
+    line = _bench_line("--steps", "2", "--warmup", "1", "--grid", str(grid), "--method", method, "--dump-outputs", str(out))
+    assert sorted(os.listdir(out)) == ["factor_sample.npy", "factor_sample_offsets.npy"]
+    sample = np.load(out / "factor_sample.npy")
+    offs = np.load(out / "factor_sample_offsets.npy")
+    assert sample.dtype == np.float64 and offs.dtype == np.float64
+    assert sample.nbytes + offs.nbytes <= 64 << 20
+
+    if method == "lu":
+        n, Cp, Ci, Cx = sf.gen.unsymmetric_stencil(grid, grid, grid, extra_per_row=0, seed=2024, drop=0.05)
+        sym = sf.analyze(n, Cp, Ci, Cx, sf.grid_nd_perm(grid, grid, grid, 3, 1), sf.REFERENCE_SLOT_1GPU, "lu", False)
+        plan = sf.LUPlan(sym)
+        plan.set_values(sym.Lx, sym.Ux)
+        plan.set_pivoting(0.1)
+    else:
+        n, Cp, Ci, Cx = sf.gen.laplacian_lower(grid, grid, grid)
+        sym = sf.analyze(n, Cp, Ci, Cx, sf.grid_nd_perm(grid, grid, grid, 3, 1), sf.REFERENCE_SLOT_1GPU)
+        plan = sf.CholPlan(sym)
+        plan.set_values(sym.Lx)
+    plan.factorize()
+    ref = plan.get_factor().copy()
+    plan.close()
+    assert line["config"]["factor_doubles"] == ref.size
+    if grid == 40:
+        assert offs.size > 1            # 32.6M entries: larger than the sample
+
+    if offs.size == 1:
+        assert offs[0] == 0 and sample.size == ref.size
+        want = ref
+    else:
+        starts = offs.astype(np.int64)
+        assert np.all(starts.astype(np.float64) == offs) and np.all(np.diff(starts) > 0)
+        assert starts[-1] < ref.size and sample.size % starts.size == 0
+        blk = sample.size // starts.size
+        assert starts[-1] + blk <= ref.size
+        want = np.concatenate([ref[b:b + blk] for b in starts])
+    assert np.max(np.abs(sample - want)) <= 1e-12 * np.max(np.abs(want))

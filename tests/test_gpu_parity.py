@@ -418,7 +418,7 @@ def test_bench_multi_gpu_code_path_on_one_rank(comm, method):
                SF_FORCE_DISTRIBUTED="1", SF_BENCH_COMM=comm)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--grid", "24",
-           "--method", method, "--cpu-grid", "0"]
+           "--method", method, "--cpu-grid", "0", "--full"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=root)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
     line = json.loads(p.stdout.strip().splitlines()[-1])

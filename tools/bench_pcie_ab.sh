@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 out=gpurun_out/bench_pcie_ab.txt; : > $out
 for cfg in "$@"; do
   for rep in 1 2 3; do
-    env $cfg timeout -k 10 200 python bench.py --steps 2 --warmup 1 --cpu-grid 0 --no-roofline --no-secondary > /tmp/pcie_ab.json 2>/dev/null || exit 1
+    env $cfg timeout -k 10 200 python bench.py --full --steps 2 --warmup 1 --cpu-grid 0 --no-roofline --no-secondary > /tmp/pcie_ab.json 2>/dev/null || exit 1
     python - "$cfg" >> $out <<'PY'
 import json, sys
 d = json.loads(open("/tmp/pcie_ab.json").read().strip().splitlines()[-1]); pc = d["config"]["pcie_inclusive"]

@@ -8,9 +8,9 @@ O=gpurun_out/$TAG
 mkdir -p $O
 for pass in "FETCH_SIZE" "WRITE_SIZE TCC_EA0_ATOMIC_sum"; do
   d=$O/c3pmc_$(echo $pass | cut -d' ' -f1)
-  rocprofv3 --pmc $pass --output-format csv -d $d -- python3 bench.py --workload stencil2d --steps 1 --warmup 0 --cpu-grid 0 --no-roofline --no-pcie > /dev/null 2> $d.err
+  rocprofv3 --pmc $pass --output-format csv -d $d -- python3 bench.py --full --workload stencil2d --steps 1 --warmup 0 --cpu-grid 0 --no-roofline --no-pcie > /dev/null 2> $d.err
 done
-python tools/summarize_pmc.py --factorizations 1 --what "rocprofv3 --pmc passes (FETCH_SIZE; WRITE_SIZE TCC_EA0_ATOMIC_sum; one pass per directory, no tracing flags) on python3 bench.py --workload stencil2d --steps 1 --warmup 0 --cpu-grid 0 --no-roofline --no-pcie (ONE factorization + one device solve + the on-device validate), summed per kernel. fetch bytes = 2 x FETCH_SIZE x 1024 (gfx950 correction)." $O/pmc_traffic_config3.json $O/c3pmc_FETCH_SIZE $O/c3pmc_WRITE_SIZE > /dev/null
+python tools/summarize_pmc.py --factorizations 1 --what "rocprofv3 --pmc passes (FETCH_SIZE; WRITE_SIZE TCC_EA0_ATOMIC_sum; one pass per directory, no tracing flags) on python3 bench.py --full --workload stencil2d --steps 1 --warmup 0 --cpu-grid 0 --no-roofline --no-pcie (ONE factorization + one device solve + the on-device validate), summed per kernel. fetch bytes = 2 x FETCH_SIZE x 1024 (gfx950 correction)." $O/pmc_traffic_config3.json $O/c3pmc_FETCH_SIZE $O/c3pmc_WRITE_SIZE > /dev/null
 rm -rf $O/c3pmc_FETCH_SIZE $O/c3pmc_WRITE_SIZE
 python - $O/pmc_traffic_config3.json <<'PY'
 import json, sys

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/../.."
 out=gpurun_out/lookahead1.txt; : > $out
 run() {  # label env...
   local label=$1; shift
-  a=$(env "$@" python bench.py --cpu-grid 0 --no-pcie --no-secondary --no-roofline --steps 6 --warmup 2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); print(d['ms_per_step'], d['config']['residual_device_solve'])")
+  a=$(env "$@" python bench.py --full --cpu-grid 0 --no-pcie --no-secondary --no-roofline --steps 6 --warmup 2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); print(d['ms_per_step'], d['config']['residual_device_solve'])")
   echo "$label 128^3: $a" | tee -a $out
 }
 run "baseline            "  SF_X=0
