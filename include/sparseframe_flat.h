@@ -96,7 +96,10 @@ typedef struct sf_chol_plan sf_chol_plan;
 
 /* Uploads the symbolic structure to `device`, builds the level schedule and the grouped
  * task tables, allocates the device-resident factor (xsize doubles).  Depends on the
- * structure only: reusable for any number of numeric factorizations of the same pattern. */
+ * structure only: reusable for any number of numeric factorizations of the same pattern.
+ * Every entry (Li[p], j) of a column j of supernode s must have a place in its panel: Super[s] <= Li[p] < n, and Li[p] is
+ * a column of s or one of the rows Lsi lists for s -- otherwise SF_ERR_ARG (for every plan constructor, LU's Ui likewise).
+ * An entry given more than once in its column is loaded from its LAST occurrence, as the reference's sequential loadA does. */
 int sf_chol_plan_create(sf_chol_plan **plan, int device,
                         sf_long n, sf_long nsuper,
                         const sf_long *Super, const sf_long *SuperMap,

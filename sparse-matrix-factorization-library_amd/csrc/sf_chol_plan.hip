@@ -331,7 +331,39 @@ static int plan_create(sf_chol_plan** out, int device, bool lu, sf_long n, sf_lo
             if (nscol <= 0 || nsrow < nscol || Lsxp[s + 1] - Lsxp[s] != want || nsrow >= (sf_long)0x7fffffff || Lsip[s] < 0) bad = true;
         }
         if (bad || Super[0] != 0 || Super[nsuper] != n) { delete p; return SF_ERR_ARG; }
-        auto check_range = [&](sf_long s0, sf_long s1) {
+        for (sf_long j = 0; j < n; ++j)
+            if (Lp[j] < 0 || Lp[j + 1] < Lp[j] || (lu && Up && Ui && (Up[j] < 0 || Up[j + 1] < Up[j]))) bad = true;
+        if (bad) { delete p; return SF_ERR_ARG; }
+        // Matrix entries: every (i, j) of column j of supernode s must have a place in its panel -- i >= Super[s], and i is a
+        // column of s or one of its rows below (the assembly kernels search the row list and would store a foreign row somewhere
+        // else).  An entry given twice resolves to the LAST one, as in the reference's sequential loadA (C:2009-2020): the earlier
+        // ones are collected in drop[] and taken out of the load map, whose entries are stored in parallel.
+        std::vector<std::vector<int64_t>> dropL_t, dropU_t;
+        auto check_entries = [&](const sf_long* Cp, const sf_long* Ci, sf_long s, std::vector<int32_t>& seen_col, std::vector<int64_t>& seen_p,
+                                 std::vector<int64_t>& drop) {
+            const sf_long c0 = Super[s], c1 = Super[s + 1], nscol = c1 - c0, nsrow = Lsip[s + 1] - Lsip[s];
+            const sf_long* below = Lsi + Lsip[s] + nscol;
+            if ((sf_long)seen_col.size() < nsrow) { seen_col.assign((size_t)nsrow, -1); seen_p.resize((size_t)nsrow); }
+            for (sf_long j = c0; j < c1; ++j) {
+                for (sf_long q = Cp[j]; q < Cp[j + 1]; ++q) {
+                    const sf_long i = Ci[q];
+                    if (i < c0 || i >= n) return false;
+                    sf_long si = i - c0;
+                    if (i >= c1) {
+                        const sf_long* it = std::lower_bound(below, below + (nsrow - nscol), i);
+                        if (it == below + (nsrow - nscol) || *it != i) return false;
+                        si = nscol + (it - below);
+                    }
+                    if (seen_col[(size_t)si] == (int32_t)j) drop.push_back(seen_p[(size_t)si]);
+                    seen_col[(size_t)si] = (int32_t)j;
+                    seen_p[(size_t)si] = q;
+                }
+            }
+            return true;
+        };
+        auto check_range = [&](sf_long s0, sf_long s1, int t) {
+            std::vector<int32_t> seen_col;
+            std::vector<int64_t> seen_p;
             for (sf_long s = s0; s < s1 && !bad.load(std::memory_order_relaxed); ++s) {
                 const sf_long nscol = Super[s + 1] - Super[s], nsrow = Lsip[s + 1] - Lsip[s];
                 for (sf_long k = 0; k < nsrow; ++k) {
@@ -342,11 +374,18 @@ static int plan_create(sf_chol_plan** out, int device, bool lu, sf_long n, sf_lo
                 // SuperMap indexes level[] / phase[] below: it must be the inverse of Super (foreign arrays: checked, not trusted)
                 for (sf_long j = Super[s]; j < Super[s + 1]; ++j)
                     if (SuperMap[j] != s) { bad = true; return; }
+                if (!check_entries(Lp, Li, s, seen_col, seen_p, dropL_t[(size_t)t])) { bad = true; return; }
+                if (lu && Up && Ui) {
+                    std::fill(seen_col.begin(), seen_col.end(), -1);
+                    if (!check_entries(Up, Ui, s, seen_col, seen_p, dropU_t[(size_t)t])) { bad = true; return; }
+                }
             }
         };
-        const int64_t work = (int64_t)Lsip[nsuper] + n;
+        const int64_t work = (int64_t)Lsip[nsuper] + n + Lp[n] + ((lu && Up && Ui) ? Up[n] : 0);
         const int T = work < (1 << 22) ? 1 : (int)std::min<unsigned>(8, std::max(1u, std::thread::hardware_concurrency()));
-        if (T == 1) check_range(0, nsuper);
+        dropL_t.resize((size_t)T);
+        dropU_t.resize((size_t)T);
+        if (T == 1) check_range(0, nsuper, 0);
         else {
             std::vector<std::thread> th;
             sf_long s0 = 0;
@@ -354,12 +393,14 @@ static int plan_create(sf_chol_plan** out, int device, bool lu, sf_long n, sf_lo
                 const int64_t upto = (int64_t)Lsip[nsuper] * (t + 1) / T;
                 sf_long s1 = (t == T - 1) ? nsuper : (sf_long)(std::upper_bound(Lsip + s0, Lsip + nsuper, (sf_long)upto) - Lsip);
                 s1 = std::min(std::max(s1, s0), nsuper);
-                th.emplace_back(check_range, s0, s1);
+                th.emplace_back(check_range, s0, s1, t);
                 s0 = s1;
             }
             for (std::thread& t : th) t.join();
         }
         if (bad) { delete p; return SF_ERR_ARG; }
+        for (auto& d : dropL_t) p->load_dropL.insert(p->load_dropL.end(), d.begin(), d.end());
+        for (auto& d : dropU_t) p->load_dropU.insert(p->load_dropU.end(), d.begin(), d.end());
     }
 
     // ---------------- levels of the supernodal tree ----------------
@@ -1415,6 +1456,20 @@ static int plan_create(sf_chol_plan** out, int device, bool lu, sf_long n, sf_lo
                 if (!dry) sf::launch_build_loadmap(p->u_alias ? p->d_Lp : p->d_Up, p->u_alias ? p->d_Li : p->d_Ui, (int32_t)n, p->d_Super, p->d_SuperMap,
                                                    p->d_Lsip, p->d_Lsi, xpm, p->xC, 0, p->d_loadmapU, p->stream);
             }
+            for (int u = 0; u < (lu ? 2 : 1) && !dry; ++u) {
+                // (U aliasing L: the U map indexes the same entries as L's, so L's superseded positions are dropped from it too)
+                const std::vector<int64_t>& drop = (u && !p->u_alias) ? p->load_dropU : p->load_dropL;
+                if (drop.empty()) continue;
+                int64_t* d_drop = nullptr;
+                if (hipMalloc((void**)&d_drop, drop.size() * sizeof(int64_t)) != hipSuccess) { rc = SF_ERR_ALLOC; break; }
+                if (hipMemcpy(d_drop, drop.data(), drop.size() * sizeof(int64_t), hipMemcpyHostToDevice) == hipSuccess)
+                    sf::launch_loadmap_drop(d_drop, (int64_t)drop.size(), u ? p->d_loadmapU : p->d_loadmapL, p->stream);
+                else rc = SF_ERR_HIP;
+                if (hipStreamSynchronize(p->stream) != hipSuccess) rc = SF_ERR_HIP;
+                (void)hipFree(d_drop);
+                if (rc) break;
+            }
+            if (rc) break;
             if (!dry && (hipStreamSynchronize(p->stream) != hipSuccess || hipGetLastError() != hipSuccess)) { rc = SF_ERR_HIP; break; }
         }
         // GEMM launches: 8 claim counters each (one per XCD) for the dynamic deal of their whole-tile rounds

@@ -102,6 +102,17 @@ k_load_mapped(const double* __restrict__ Lx, const int64_t* __restrict__ map, in
     }
 }
 
+__global__ void __launch_bounds__(256)
+k_loadmap_drop(const int64_t* __restrict__ drop, int64_t count, int64_t* __restrict__ map) {
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += (int64_t)gridDim.x * blockDim.x) map[drop[k]] = -1;
+}
+
+void launch_loadmap_drop(const int64_t* drop, int64_t count, int64_t* map, hipStream_t st) {
+    if (count <= 0) return;
+    const int64_t blocks = std::min<int64_t>((count + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_loadmap_drop, dim3((unsigned)blocks), dim3(256), 0, st, drop, count, map);
+}
+
 void launch_build_loadmap(const int64_t* Lp, const int32_t* Li, int32_t n, const int32_t* Super, const int32_t* SuperMap,
                           const int64_t* Lsip, const int32_t* Lsi, const int64_t* Lsxp, int64_t base, int skip_diag, int64_t* map, hipStream_t st) {
     if (n <= 0) return;
@@ -1384,13 +1395,13 @@ k_gemm(const GemmProb* __restrict__ probs, const GemmTask* __restrict__ tasks,
 // The updated 64 x 64 tile then goes to LDS (U[column][row]) where the POTRF wave / the blocked solve picks it up.
 // ---------------------------------------------------------------------------------------------------
 #ifndef SF_LU_STEP_WGS
-#define SF_LU_STEP_WGS 3
+#define SF_LU_STEP_WGS 3      // workgroups per CU the LU variant of k_step is compiled for (168 VGPRs; the throughput-bound launches of the lower levels want the third)
+#endif
 #ifndef SF_GEMM_MIN_UNITS_DEFAULT
 #define SF_GEMM_MIN_UNITS_DEFAULT 16     // 16-deep K steps; swept in round 4: config 3 11.20 -> 10.99 ms, config 5 and 128^3 unchanged (tools/experiments/gemm_min_units.sh)
 #endif
 #ifndef SF_POTRF_PW
 #define SF_POTRF_PW 16        // columns per panel of the fused step's 64 x 64 POTRF (16 or 32; 32 measured slower, see k_step)
-#endif      // workgroups per CU the LU variant of k_step is compiled for (168 VGPRs; the throughput-bound launches of the lower levels want the third)
 #endif
 constexpr int ST_ULD = ST_ROWS + 1;      // LDS column stride of the updated tile U[c][r]
 constexpr int ST_KC = 32;                // K chunk of the update's LDS-staged operand

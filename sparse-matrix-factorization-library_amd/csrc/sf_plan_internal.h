@@ -218,6 +218,7 @@ struct sf_chol_plan {
     bool own_stream = true;
     int8_t* d_loadmask = nullptr;
     int64_t *d_loadmapL = nullptr, *d_loadmapU = nullptr;      // whole plans: offset into d_Lsx of every entry of L (/ U), -1 = not loaded
+    std::vector<int64_t> load_dropL, load_dropU;   // entries given again later in their column (the last one is loaded): -1 in the load map
     // device solve (Cholesky, whole matrix on one device): task lists per (level, 64-column step)
     sf::SolveTask* d_solve = nullptr;
     // backward sweep: row-major copies of the diagonal blocks of the top levels' steps (made at the start of every solve)

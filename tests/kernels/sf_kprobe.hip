@@ -1,0 +1,216 @@
+// Test-only probe: thin extern "C" wrappers around the sf::launch_* entry points of libsparseframe_hip.so, so that the
+// tests can run ONE kernel launch on task lists they build themselves.  Each wrapper copies a host image of a double arena
+// (and the task arrays, maps, flags, pivot records) to the device, launches once, synchronises, and copies the arena and
+// the outputs back.  No numerical logic lives here; tests/kernel_ref.py and tests/test_kernels.py do the rest.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "sf_kernels.h"
+
+namespace {
+
+// device copies of host arrays, freed on scope exit; the first failing HIP call is kept in `rc`
+struct Dev {
+    std::vector<void*> ptrs;
+    hipError_t rc = hipSuccess;
+    ~Dev() { for (void* p : ptrs) (void)hipFree(p); }
+    template <class T> T* in(const T* h, int64_t count) {
+        if (rc != hipSuccess || count <= 0) return nullptr;
+        void* d = nullptr;
+        if ((rc = hipMalloc(&d, (size_t)count * sizeof(T))) != hipSuccess) return nullptr;
+        ptrs.push_back(d);
+        if (h) rc = hipMemcpy(d, h, (size_t)count * sizeof(T), hipMemcpyHostToDevice);
+        else rc = hipMemset(d, 0, (size_t)count * sizeof(T));
+        return (T*)d;
+    }
+    template <class T> void out(T* h, const T* d, int64_t count) {
+        if (rc == hipSuccess && h && d && count > 0) rc = hipMemcpy(h, d, (size_t)count * sizeof(T), hipMemcpyDeviceToHost);
+    }
+    void finish() {
+        if (rc != hipSuccess) return;
+        rc = hipGetLastError();
+        if (rc == hipSuccess) rc = hipDeviceSynchronize();
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int kp_sizeof(const char* name) {
+    if (!strcmp(name, "GemmProb")) return (int)sizeof(sf::GemmProb);
+    if (!strcmp(name, "GemmTask")) return (int)sizeof(sf::GemmTask);
+    if (!strcmp(name, "PotrfTask")) return (int)sizeof(sf::PotrfTask);
+    if (!strcmp(name, "TrsmTask")) return (int)sizeof(sf::TrsmTask);
+    if (!strcmp(name, "StepTask")) return (int)sizeof(sf::StepTask);
+    return -1;
+}
+
+int kp_free_mem(int64_t* free_bytes) {
+    size_t f = 0, t = 0;
+    const hipError_t rc = hipMemGetInfo(&f, &t);
+    *free_bytes = (int64_t)f;
+    return (int)rc;
+}
+
+int kp_gemm(double* arena, int64_t narena, const sf::GemmProb* probs, int nprobs, const sf::GemmTask* tasks, int ntasks,
+            const uint32_t* kt_prefix, uint32_t u_lo, uint32_t u_hi, int mode, const int32_t* relmap, int64_t nrel,
+            int use_ticket, int whole_tiles, int grid_cap) {
+    Dev d;
+    double* A = d.in(arena, narena);
+    const sf::GemmProb* P = d.in(probs, nprobs);
+    const sf::GemmTask* T = d.in(tasks, ntasks);
+    const uint32_t* K = d.in(kt_prefix, (int64_t)ntasks + 1);
+    const int32_t* R = d.in(relmap, nrel);
+    int* tk = use_ticket ? d.in<int>(nullptr, 8) : nullptr;
+    if (d.rc == hipSuccess) sf::launch_gemm(P, T, K, ntasks, u_lo, u_hi, mode, A, R, tk, 0, whole_tiles, grid_cap);
+    d.finish();
+    d.out(arena, A, narena);
+    return (int)d.rc;
+}
+
+int kp_update_small(double* arena, int64_t narena, const sf::GemmProb* probs, int nprobs, const sf::GemmTask* tasks, int ntasks,
+                    const int32_t* relmap, int64_t nrel) {
+    Dev d;
+    double* A = d.in(arena, narena);
+    const sf::GemmProb* P = d.in(probs, nprobs);
+    const sf::GemmTask* T = d.in(tasks, ntasks);
+    const int32_t* R = d.in(relmap, nrel);
+    if (d.rc == hipSuccess) sf::launch_update_small(P, T, ntasks, A, R, 0);
+    d.finish();
+    d.out(arena, A, narena);
+    return (int)d.rc;
+}
+
+int kp_build_relmaps(const sf::GemmProb* probs, int nprobs, const int32_t* Lsi, int64_t nLsi, int32_t* relmap, int64_t nrel) {
+    Dev d;
+    const sf::GemmProb* P = d.in(probs, nprobs);
+    const int32_t* L = d.in(Lsi, nLsi);
+    int32_t* R = d.in(relmap, nrel);
+    if (d.rc == hipSuccess) sf::launch_build_relmaps(P, nprobs, L, R, 0);
+    d.finish();
+    d.out(relmap, R, nrel);
+    return (int)d.rc;
+}
+
+int kp_potrf(double* arena, int64_t narena, const sf::PotrfTask* tasks, int ntasks, int* info) {
+    Dev d;
+    double* A = d.in(arena, narena);
+    const sf::PotrfTask* T = d.in(tasks, ntasks);
+    int* I = d.in(info, 1);
+    if (d.rc == hipSuccess) sf::launch_potrf(T, ntasks, A, I, 0);
+    d.finish();
+    d.out(arena, A, narena);
+    d.out(info, I, 1);
+    return (int)d.rc;
+}
+
+// pivpos / pivinv: npiv entries each, or null (tol == 0: no record); nperturb: one counter
+int kp_getrf(double* arena, int64_t narena, const sf::PotrfTask* tasks, int ntasks, int64_t u_shift, int* info, double tol, double eps,
+             int32_t* pivpos, int32_t* pivinv, int64_t npiv, int* nperturb) {
+    Dev d;
+    double* A = d.in(arena, narena);
+    const sf::PotrfTask* T = d.in(tasks, ntasks);
+    int* I = d.in(info, 1);
+    int32_t* pp = pivpos ? d.in(pivpos, npiv) : nullptr;
+    int32_t* pi = pivinv ? d.in(pivinv, npiv) : nullptr;
+    int* np = d.in(nperturb, 1);
+    if (d.rc == hipSuccess) sf::launch_getrf(T, ntasks, A, u_shift, I, sf::PivotCtl{tol, eps, pp, pi, np}, 0);
+    d.finish();
+    d.out(arena, A, narena);
+    d.out(info, I, 1);
+    d.out(pivpos, pp, npiv);
+    d.out(pivinv, pi, npiv);
+    d.out(nperturb, np, 1);
+    return (int)d.rc;
+}
+
+int kp_trsm(double* arena, int64_t narena, const sf::TrsmTask* tasks, int ntasks, const int32_t* pivinv, int64_t npiv) {
+    Dev d;
+    double* A = d.in(arena, narena);
+    const sf::TrsmTask* T = d.in(tasks, ntasks);
+    const int32_t* pi = pivinv ? d.in(pivinv, npiv) : nullptr;
+    if (d.rc == hipSuccess) sf::launch_trsm(T, ntasks, A, pi, 0);
+    d.finish();
+    d.out(arena, A, narena);
+    return (int)d.rc;
+}
+
+// flags: nflags words, in and out (a second launch with epoch + 1 re-uses them); tinv: ntinv doubles of scratch
+int kp_step(double* arena, int64_t narena, const sf::StepTask* tasks, int ntasks, int lu, int* flags, int nflags, int epoch, int* info,
+            int64_t ntinv, double tol, double eps, int32_t* pivpos, int32_t* pivinv, int64_t npiv, int* nperturb) {
+    Dev d;
+    double* A = d.in(arena, narena);
+    const sf::StepTask* T = d.in(tasks, ntasks);
+    int* F = d.in(flags, nflags);
+    int* I = d.in(info, 1);
+    double* tinv = d.in<double>(nullptr, ntinv);
+    int* tk = d.in<int>(nullptr, 1);
+    int32_t* pp = pivpos ? d.in(pivpos, npiv) : nullptr;
+    int32_t* pi = pivinv ? d.in(pivinv, npiv) : nullptr;
+    int* np = d.in(nperturb, 1);
+    if (d.rc == hipSuccess) sf::launch_step(T, ntasks, lu, A, F, epoch, I, tinv, tk, sf::PivotCtl{tol, eps, pp, pi, np}, 0);
+    d.finish();
+    d.out(arena, A, narena);
+    d.out(flags, F, nflags);
+    d.out(info, I, 1);
+    d.out(pivpos, pp, npiv);
+    d.out(pivinv, pi, npiv);
+    d.out(nperturb, np, 1);
+    return (int)d.rc;
+}
+
+int kp_build_loadmap(const int64_t* Lp, const int32_t* Li, int32_t n, const int32_t* Super, const int32_t* SuperMap, int32_t nsuper,
+                     const int64_t* Lsip, const int32_t* Lsi, const int64_t* Lsxp, int64_t base, int skip_diag, int64_t* map) {
+    Dev d;
+    const int64_t nnz = Lp[n];
+    const int64_t* dLp = d.in(Lp, (int64_t)n + 1);
+    const int32_t* dLi = d.in(Li, nnz);
+    const int32_t* dS = d.in(Super, (int64_t)nsuper + 1);
+    const int32_t* dSM = d.in(SuperMap, n);
+    const int64_t* dLsip = d.in(Lsip, (int64_t)nsuper + 1);
+    const int32_t* dLsi = d.in(Lsi, Lsip[nsuper]);
+    const int64_t* dLsxp = d.in(Lsxp, (int64_t)nsuper + 1);
+    int64_t* dmap = d.in(map, nnz);
+    if (d.rc == hipSuccess) sf::launch_build_loadmap(dLp, dLi, n, dS, dSM, dLsip, dLsi, dLsxp, base, skip_diag, dmap, 0);
+    d.finish();
+    d.out(map, dmap, nnz);
+    return (int)d.rc;
+}
+
+int kp_load_mapped(double* arena, int64_t narena, const double* Lx, const int64_t* map, int64_t nnz) {
+    Dev d;
+    double* A = d.in(arena, narena);
+    const double* dLx = d.in(Lx, nnz);
+    const int64_t* dmap = d.in(map, nnz);
+    if (d.rc == hipSuccess) sf::launch_load_mapped(dLx, dmap, nnz, A, 0);
+    d.finish();
+    d.out(arena, A, narena);
+    return (int)d.rc;
+}
+
+// load_mask: nsuper bytes, or null
+int kp_load_panels(double* arena, int64_t narena, const int64_t* Lp, const int32_t* Li, const double* Lx, int32_t n,
+                   const int32_t* Super, const int32_t* SuperMap, int32_t nsuper, const int64_t* Lsip, const int32_t* Lsi,
+                   const int64_t* Lsxp, int skip_diag, const int8_t* load_mask) {
+    Dev d;
+    const int64_t nnz = Lp[n];
+    double* A = d.in(arena, narena);
+    const int64_t* dLp = d.in(Lp, (int64_t)n + 1);
+    const int32_t* dLi = d.in(Li, nnz);
+    const double* dLx = d.in(Lx, nnz);
+    const int32_t* dS = d.in(Super, (int64_t)nsuper + 1);
+    const int32_t* dSM = d.in(SuperMap, n);
+    const int64_t* dLsip = d.in(Lsip, (int64_t)nsuper + 1);
+    const int32_t* dLsi = d.in(Lsi, Lsip[nsuper]);
+    const int64_t* dLsxp = d.in(Lsxp, (int64_t)nsuper + 1);
+    const int8_t* dmask = load_mask ? d.in(load_mask, nsuper) : nullptr;
+    if (d.rc == hipSuccess) sf::launch_load_panels(dLp, dLi, dLx, n, dS, dSM, dLsip, dLsi, dLsxp, A, skip_diag, dmask, 0);
+    d.finish();
+    d.out(arena, A, narena);
+    return (int)d.rc;
+}
+
+}  // extern "C"
