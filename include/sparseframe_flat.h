@@ -124,6 +124,13 @@ int sf_chol_plan_factorize_to_host(sf_chol_plan *plan, const sf_float *Lx, const
 void *sf_chol_plan_factor_device_ptr(sf_chol_plan *plan);
 /* device-side supernodal solve with the resident factor: x <- (L L^T)^{-1} b, permuted space */
 int sf_chol_plan_solve(sf_chol_plan *plan, const sf_float *b_host, sf_float *x_host);
+/* device-side supernodal solve of nrhs right-hand sides with the resident factor, permuted space: X <- (L L^T)^{-1} B
+ * (LU plans: (L U)^{-1} B, with the plan's pivots when pivoting is on).  B, X: column-major host arrays, leading dimensions
+ * ldb, ldx >= n; X may be B (ldx == ldb).  nrhs == 0: no-op.  Whole, resident plans only (partial, sharded, mapped,
+ * out-of-core and schedule-only plans: SF_ERR_ARG).  16 right-hand sides per sweep (stat "solve_many_width"); the device
+ * block is allocated by the first call and kept (stat "bytes_solve_many", not in "bytes_device"); "last_solve_many_ms":
+ * device time of the sweeps of the last call, copies excluded. */
+int sf_chol_plan_solve_many(sf_chol_plan *plan, sf_long nrhs, const sf_float *B, sf_long ldb, sf_float *X, sf_long ldx);
 /* values [e_begin, e_end) of the factor in the reference layout (whole plans only) */
 int sf_chol_plan_get_factor_range(sf_chol_plan *plan, sf_long e_begin, sf_long e_end, sf_float *out);
 /* SparseFrame_validate on the device (C:3141-3266; LU plans: L:3702-3858): b_i = 1 + i/n, solve with the resident factor,
@@ -344,6 +351,8 @@ int sf_lu_plan_sync(sf_lu_plan *plan);
 int sf_lu_plan_get_factor(sf_lu_plan *plan, sf_float *Lsx);
 /* device-side solve with the resident factors: x <- (L U)^{-1} b, permuted space (device twin of L:3592-3700) */
 int sf_lu_plan_solve(sf_lu_plan *plan, const sf_float *b_host, sf_float *x_host);
+/* sf_chol_plan_solve_many for an LU plan: X <- (L U)^{-1} B, the plan's pivots applied when pivoting is on */
+int sf_lu_plan_solve_many(sf_lu_plan *plan, sf_long nrhs, const sf_float *B, sf_long ldb, sf_float *X, sf_long ldx);
 double sf_lu_plan_stat(const sf_lu_plan *plan, const char *name);
 int sf_lu_plan_set_profiling(sf_lu_plan *plan, int on);
 int sf_lu_plan_destroy(sf_lu_plan *plan);

@@ -84,6 +84,8 @@ lib.sf_chol_plan_factor_device_ptr.argtypes = [C.c_void_p]
 lib.sf_chol_plan_factor_device_ptr.restype = C.c_void_p
 lib.sf_chol_plan_solve.argtypes = [C.c_void_p, c_double_p, c_double_p]
 lib.sf_chol_plan_solve.restype = C.c_int
+lib.sf_chol_plan_solve_many.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64]
+lib.sf_chol_plan_solve_many.restype = C.c_int
 lib.sf_chol_plan_solve_distributed.argtypes = [C.c_void_p, C.c_void_p, c_double_p, c_double_p]
 lib.sf_chol_plan_solve_distributed.restype = C.c_int
 lib.sf_handlers_replica_mismatches.argtypes = [C.c_void_p]
@@ -219,6 +221,8 @@ lib.sf_lu_plan_get_factor.argtypes = [C.c_void_p, c_double_p]
 lib.sf_lu_plan_get_factor.restype = C.c_int
 lib.sf_lu_plan_solve.argtypes = [C.c_void_p, c_double_p, c_double_p]
 lib.sf_lu_plan_solve.restype = C.c_int
+lib.sf_lu_plan_solve_many.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64]
+lib.sf_lu_plan_solve_many.restype = C.c_int
 lib.sf_lu_plan_stat.argtypes = [C.c_void_p, C.c_char_p]
 lib.sf_lu_plan_stat.restype = C.c_double
 lib.sf_lu_plan_set_profiling.argtypes = [C.c_void_p, C.c_int]

@@ -193,6 +193,20 @@ void launch_solve_bwd(const SolveTask* t, int nt, int big, const double* Lsx, co
 // row-major copies of the diagonal blocks of the backward diagonal tasks list[0 .. ntasks) (indices into `tasks`) into T
 void launch_solve_transpose_diag(const SolveTask* tasks, const int64_t* list, int64_t ntasks, const double* Lsx, double* T, hipStream_t st);
 
+// ---- multi-right-hand-side twins (sf_chol_plan_solve_many): the same tasks, schedule and sync words, SVM_W right-hand sides per
+// sweep, x an n x SVM_W block stored ROW-major (x[i * SVM_W + c]; see sf_kernels.hip).  16 = the N of v_mfma_f64_16x16x4f64.
+constexpr int SVM_W = 16;
+void launch_solve_many_small_fwd(const SolveTask* t, int nt, const double* Lsx, const int32_t* Lsi, double* x, int unit,
+                                 const int32_t* pivpos, hipStream_t st);
+void launch_solve_many_small_bwd(const SolveTask* t, int nt, const double* Lsx, const int32_t* Lsi, double* x, hipStream_t st);
+void launch_solve_many_fwd(const SolveTask* t, int nt, int big, const double* Lsx, const int32_t* Lsi, double* x, int unit,
+                           const int32_t* pivpos, int* sync, int* ticket, int* info, hipStream_t st);
+void launch_solve_many_bwd(const SolveTask* t, int nt, int big, const double* Lsx, const int32_t* Lsi, double* x, int* sync, int* ticket,
+                           int* info, hipStream_t st, const double* Tbase = nullptr);
+// column-major n x cw (leading dimension n) -> row-major n x SVM_W, columns [cw, SVM_W) zero; and back (columns [0, cw) only)
+void launch_solve_many_pack(const double* Bc, int64_t n, int cw, double* X, hipStream_t st);
+void launch_solve_many_unpack(const double* X, int64_t n, int cw, double* Bc, hipStream_t st);
+
 void launch_noop(hipStream_t st);
 
 // device twin of SparseFrame_validate's residual (C:3182-3263): b_i = 1 + i/n is written to b, r = A x - b, the four maxima

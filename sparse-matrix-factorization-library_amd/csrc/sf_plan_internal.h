@@ -241,6 +241,11 @@ struct sf_chol_plan {
     int n_solve_sync = 0;
     std::vector<SolveStep> solve_steps;
     double last_solve_ms = 0;
+    // sf_chol_plan_solve_many: the n x SVM_W row-major block and an n x SVM_W column-major staging buffer for the copies, one
+    // allocation made by the first call (not in bytes_device)
+    double* d_xm = nullptr;
+    size_t bytes_solve_many = 0;
+    double last_solve_many_ms = 0;
     int device = 0;
     int64_t n = 0, nsuper = 0, nnz = 0, isize = 0, xsize = 0;
     hipStream_t stream = nullptr;

@@ -1,0 +1,94 @@
+"""The multi-right-hand-side solve's C ABI without a device: exported symbols, argument checks that run before anything
+touches a device, and zero scratch for the new solve kernels."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from util import sf, gen, nd_perm_py
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "sparse-matrix-factorization-library_amd", "libsparseframe_hip.so")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+SF_ERR_ARG = 1
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def test_symbols_exported():
+    nm = subprocess.run(["nm", "-D", LIB], stdout=subprocess.PIPE, text=True).stdout
+    for name in ("sf_chol_plan_solve_many", "sf_lu_plan_solve_many"):
+        assert f" T {name}" in nm
+
+
+def test_err_arg_constant():
+    assert sf.lib.sf_chol_plan_solve_many(None, 1, None, 1, None, 1) == SF_ERR_ARG
+
+
+def _schedule(lu):
+    N = 8
+    if lu:
+        n, Cp, Ci, Cx = gen.unsymmetric_stencil(N, N, N, seed=5)
+        sym = sf.analyze(n, Cp, Ci, Cx, nd_perm_py(N, N, N), 1 << 30, "lu", False)
+    else:
+        n, Cp, Ci, Cx = gen.laplacian_lower(N, N, N)
+        sym = sf.analyze(n, Cp, Ci, Cx, sf.grid_nd_perm(N, N, N), 1 << 30)
+    return sym, sf.Schedule(sym, np.zeros(sym.nsuper, dtype=np.int32), 0, 1, lu=lu)
+
+
+@pytest.mark.parametrize("lu", [False, True], ids=["cholesky", "lu"])
+def test_argument_checks(lu):
+    sym, sch = _schedule(lu)
+    fn = sf.lib.sf_lu_plan_solve_many if lu else sf.lib.sf_chol_plan_solve_many
+    n = sym.n
+    B = np.ones((n, 3), order="F")
+    X = np.empty_like(B)
+    assert fn(None, 3, _dp(B), n, _dp(X), n) == SF_ERR_ARG                 # NULL plan
+    assert fn(sch._h, -1, _dp(B), n, _dp(X), n) == SF_ERR_ARG              # nrhs < 0
+    assert fn(sch._h, 3, _dp(B), n - 1, _dp(X), n) == SF_ERR_ARG           # ldb < n
+    assert fn(sch._h, 3, _dp(B), n, _dp(X), n - 1) == SF_ERR_ARG           # ldx < n
+    assert fn(sch._h, 3, None, n, _dp(X), n) == SF_ERR_ARG                 # NULL B
+    assert fn(sch._h, 3, _dp(B), n, None, n) == SF_ERR_ARG                 # NULL X
+    assert fn(sch._h, 3, _dp(B), n, _dp(X), n) == SF_ERR_ARG               # schedule-only plan
+    assert fn(sch._h, 0, _dp(B), n, _dp(X), n) == SF_ERR_ARG               # ... even with nothing to solve
+    if not lu:
+        # an LU entry point refuses a Cholesky plan
+        assert sf.lib.sf_lu_plan_solve_many(sch._h, 3, _dp(B), n, _dp(X), n) == SF_ERR_ARG
+    sch.close()
+
+
+def test_out_of_core_schedule_refused():
+    N = 8
+    n, Cp, Ci, Cx = gen.laplacian_lower(N, N, N)
+    sym = sf.analyze(n, Cp, Ci, Cx, sf.grid_nd_perm(N, N, N), 1 << 30)
+    sch = sf.Schedule(sym, None, 0, 1, ooc_group=np.zeros(sym.nsuper, dtype=np.int32), ooc_ngroups=1)
+    B = np.ones((n, 2), order="F")
+    assert sf.lib.sf_chol_plan_solve_many(sch._h, 2, _dp(B), n, _dp(B), n) == SF_ERR_ARG
+    sch.close()
+
+
+def test_solve_many_kernels_use_no_scratch(tmp_path):
+    """sf_kernels.hip compiled device-only for gfx950: every multi-right-hand-side solve kernel reports zero scratch"""
+    src = os.path.join(ROOT, "sparse-matrix-factorization-library_amd", "csrc", "sf_kernels.hip")
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "--cuda-device-only", "-c", "-O3", "-std=c++17", "-munsafe-fp-atomics",
+                        "-I" + os.path.join(ROOT, "include"), "-Rpass-analysis=kernel-resource-usage", src, "-o", str(tmp_path / "k.o")],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-4000:]
+    scratch = {}
+    name = None
+    for line in r.stdout.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            continue
+        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
+        if m and name:
+            scratch[name] = int(m.group(1))
+    many = {k: v for k, v in scratch.items() if "k_solve_many" in k}
+    assert len(many) == 8, sorted(many)         # fwd / bwd x (BIG, not BIG), small fwd / bwd, pack, unpack
+    assert all(v == 0 for v in many.values()), many
