@@ -133,6 +133,20 @@ int sf_chol_plan_solve(sf_chol_plan *plan, const sf_float *b_host, sf_float *x_h
 int sf_chol_plan_solve_many(sf_chol_plan *plan, sf_long nrhs, const sf_float *B, sf_long ldb, sf_float *X, sf_long ldx);
 /* values [e_begin, e_end) of the factor in the reference layout (whole plans only) */
 int sf_chol_plan_get_factor_range(sf_chol_plan *plan, sf_long e_begin, sf_long e_end, sf_float *out);
+/* selected inversion: Sigma = A^{-1} = (L L^T)^{-1} on the pattern of L, permuted space, into a plan-owned device arena with the
+ * factor's reference layout (xsize doubles, panel s at Lsxp[s], nsrow x nscol column-major; the strict upper part of each
+ * diagonal block holds the mirror of its lower part).  Synchronous.  The arena and its scratch are allocated by the first call and
+ * kept until destroy (stat "bytes_selinv", not in "bytes_device"); SF_ERR_ALLOC leaves the plan usable.  Needs a successful
+ * factorization of the current values; whole, resident Cholesky plans only (schedule-only, partial, sharded, mapped, out-of-core
+ * and LU plans: SF_ERR_ARG).  Stats: "last_selinv_ms" (device time), "flops_selinv" (operation count of the unit decomposition),
+ * "selinv_valid" (1 while the arena belongs to the resident factor: set_values, a factorization or an import clear it). */
+int sf_chol_plan_selinv(sf_chol_plan *plan);
+/* arena values [e_begin, e_end) (SF_ERR_ARG when the arena is not valid) */
+int sf_chol_plan_get_selinv_range(sf_chol_plan *plan, sf_long e_begin, sf_long e_end, sf_float *out);
+/* diag(Sigma), n doubles, gathered on the device (SF_ERR_ARG when the arena is not valid) */
+int sf_chol_plan_selinv_diag(sf_chol_plan *plan, sf_float *d);
+/* log det A = 2 sum_j log L_jj of the resident factor, reduced on the device in a fixed order (independent of selinv) */
+int sf_chol_plan_logdet(sf_chol_plan *plan, sf_float *out);
 /* SparseFrame_validate on the device (C:3141-3266; LU plans: L:3702-3858): b_i = 1 + i/n, solve with the resident factor,
  * r = A x - b from the plan's copy of the matrix values, *residual = |r|_inf / (|A|_1 |x|_inf + |b|_inf).  x_host may be NULL. */
 int sf_chol_plan_validate(sf_chol_plan *plan, sf_float *residual, sf_float *x_host);

@@ -479,6 +479,29 @@ class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin):
         """X = A^-1 B for an (n, k) block of right-hand sides (any memory order), permuted space, 16 columns per device sweep"""
         return _solve_many(lib.sf_chol_plan_solve_many, "sf_chol_plan_solve_many", self._h, self.n, B)
 
+    def selinv(self):
+        """selected inversion: A^-1 on the pattern of L into a device arena (permuted space), from the resident factor"""
+        check(lib.sf_chol_plan_selinv(self._h), "sf_chol_plan_selinv")
+
+    def get_selinv(self, out=None):
+        """D2H of the selected inverse in the factor's layout (diagonal blocks full symmetric)"""
+        if out is None:
+            out = np.zeros(max(self.xsize, 1), dtype=np.float64)
+        check(lib.sf_chol_plan_get_selinv_range(self._h, 0, self.xsize, _dp(out)), "sf_chol_plan_get_selinv_range")
+        return out[:self.xsize]
+
+    def selinv_diag(self):
+        """diag(A^-1), permuted space, gathered on the device"""
+        d = np.zeros(max(self.n, 1), dtype=np.float64)
+        check(lib.sf_chol_plan_selinv_diag(self._h, _dp(d)), "sf_chol_plan_selinv_diag")
+        return d[:self.n]
+
+    def logdet(self):
+        """log det A = 2 sum log L_jj of the resident factor"""
+        out = np.zeros(1, dtype=np.float64)
+        check(lib.sf_chol_plan_logdet(self._h, _dp(out)), "sf_chol_plan_logdet")
+        return float(out[0])
+
     def stat(self, name):
         return float(lib.sf_chol_plan_stat(self._h, name.encode()))
 

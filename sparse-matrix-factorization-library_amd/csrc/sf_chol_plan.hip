@@ -82,7 +82,8 @@ int sf_chol_plan_destroy(sf_chol_plan* p) {
     (void)hipSetDevice(p->device);
     void* ptrs[] = {p->d_Lp, p->d_Li, p->d_Lx, p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, p->d_Lsxp,
                     p->d_Lsx, p->d_info, p->d_potrf, p->d_trsm, p->d_steps, p->d_flags, p->d_tinv, p->d_probs, p->d_gtasks, p->d_stasks, p->d_ktprefix,
-                    p->d_Up, p->d_Ui, p->d_Ux, p->d_Xp, p->d_pack, p->d_piv, p->d_resid, p->d_loadmask, p->d_loadmapL, p->d_loadmapU, p->d_solve, p->d_solve_sync, p->d_x, p->d_relmap, p->d_scratch, p->d_status, p->d_fill, p->d_solveT, p->d_solveT_list, p->d_xm};
+                    p->d_Up, p->d_Ui, p->d_Ux, p->d_Xp, p->d_pack, p->d_piv, p->d_resid, p->d_loadmask, p->d_loadmapL, p->d_loadmapU, p->d_solve, p->d_solve_sync, p->d_x, p->d_relmap, p->d_scratch, p->d_status, p->d_fill, p->d_solveT, p->d_solveT_list, p->d_xm,
+                    p->d_sel, p->d_sel_diag, p->d_sel_units, p->d_sel_pairs, p->d_sel_scratch};
     for (void* q : ptrs)
         if (q && !(q == (void*)p->d_Lsx && p->factor_borrowed)) (void)hipFree(q);      // (a borrowed factor buffer goes back to its lender)
     if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
@@ -822,6 +823,9 @@ static int plan_create(sf_chol_plan** out, int device, bool lu, sf_long n, sf_lo
                 g.tgt_nscol = a_nscol;
                 g.tgt_nbelow = a_nsrow - a_nscol;
                 g.map_off = relmap_size;            // one relative map per (s, a) pair, shared by the L and U^T sides
+                p->sel_pair_J.push_back((int32_t)s);        // (the pair table of the selected inversion)
+                p->sel_pair_i.push_back(i);
+                p->sel_pair_off.push_back(relmap_size);
                 relmap_size += dnm;
                 scatter_probs.push_back((int64_t)probs.size());
                 for (int side = 0; side < (lu ? 2 : 1); ++side) {
@@ -1681,6 +1685,7 @@ int sf_chol_plan_set_values(sf_chol_plan* p, const sf_float* Lx) {
     if (p->nnz > 0) HIP_TRY(hipMemcpyAsync(p->d_Lx, Lx, p->nnz * sizeof(double), hipMemcpyHostToDevice, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     p->values_set = true;
+    ++p->factor_gen;        // the resident factor (and a selected inverse from it) no longer belongs to the values
     return SF_OK;
 }
 
@@ -1706,6 +1711,7 @@ int sf_lu_plan_set_values(sf_lu_plan* p, const sf_float* Lx, const sf_float* Ux)
     }
     HIP_TRY(hipStreamSynchronize(p->stream));
     p->values_set = true;
+    ++p->factor_gen;
     return SF_OK;
 }
 
@@ -1723,6 +1729,7 @@ int sf_chol_plan_sync(sf_chol_plan* p) {
     if (p->lu) HIP_TRY(hipMemcpy(&p->last_perturbed, p->d_piv + 2 * std::max<int64_t>(p->n, 1), sizeof(int), hipMemcpyDeviceToHost));
     // 1: non-positive / zero pivot; 2: a fused step's flag wait timed out (internal error, never seen)
     p->last_status = (info & 2) ? SF_ERR_HIP : (info ? SF_ERR_NOT_POSDEF : SF_OK);
+    if (p->last_status == SF_OK && p->fact_done) p->ok_gen = p->fact_gen;
     return p->last_status;
 }
 
@@ -1783,6 +1790,8 @@ static int run_launches(sf_chol_plan* p, size_t l0, size_t l1, bool first, bool 
         if (!p->capturing) HIP_TRY(hipEventRecord(p->ev0, st));
         p->packed_pending = -1;
         p->epoch = (p->epoch == 0x7fffffff) ? 1 : p->epoch + 1;     // flag value of this factorization's fused steps (never 0)
+        p->fact_gen = ++p->factor_gen;
+        p->fact_done = false;
         if (p->capturing) {
             // a captured factorization is replayed with the SAME kernel arguments: its flag value is fixed (never seen in the array
             // again: epochs only grow) and the flags are cleared by a node of the graph itself
@@ -1920,6 +1929,7 @@ static int run_launches(sf_chol_plan* p, size_t l0, size_t l1, bool first, bool 
         }
         if (dump) fclose(dump);
     }
+    if (last) p->fact_done = true;
     if (sync) {
         if (!last) { HIP_TRY(hipStreamSynchronize(st)); return SF_OK; }
         return sf_chol_plan_sync(p);
@@ -2103,6 +2113,7 @@ int sf_plan_import_from(sf_chol_plan* dst, sf_chol_plan* const* parts, int npart
     dst->piv_tol = parts[0]->piv_tol;
     dst->piv_perturb = parts[0]->piv_perturb;
     dst->hash_epoch = -1;           // the factor changed without a factorization of dst's own: cached fingerprints are stale
+    dst->ok_gen = ++dst->factor_gen;        // ... and so is a selected inverse; the imported factor counts as factorized
     HIP_TRY(hipStreamSynchronize(dst->stream));
     return SF_OK;
 }
@@ -2226,7 +2237,11 @@ static int factorize_graph(sf_chol_plan* p, int sync) {
     }
     // (the captured kernels compare the flags with graph_epoch and the graph clears the flags itself; p->epoch stays what it is for
     //  everybody else -- the generation of the factor on the device -- and moves on with every replay)
-    if (!fresh) p->epoch = (p->epoch == 0x7fffffff) ? 1 : p->epoch + 1;
+    if (!fresh) {
+        p->epoch = (p->epoch == 0x7fffffff) ? 1 : p->epoch + 1;
+        p->fact_gen = ++p->factor_gen;
+        p->fact_done = true;
+    }
     p->packed_pending = -1;
     HIP_TRY(hipEventRecord(p->ev0, p->stream));
     HIP_TRY(hipGraphLaunch(p->graph_exec, p->stream));
@@ -2760,6 +2775,10 @@ double sf_chol_plan_stat(const sf_chol_plan* p, const char* name) {
     if (k == "last_solve_many_ms") return p->last_solve_many_ms;
     if (k == "bytes_solve_many") return (double)p->bytes_solve_many;
     if (k == "solve_many_width") return (double)sf::SVM_W;
+    if (k == "bytes_selinv") return (double)p->bytes_selinv;
+    if (k == "last_selinv_ms") return p->last_selinv_ms;
+    if (k == "flops_selinv") return p->flops_selinv;
+    if (k == "selinv_valid") return (p->d_sel && p->sel_gen == p->factor_gen) ? 1.0 : 0.0;
     if (k == "perturbed_pivots") return (double)p->last_perturbed;
     if (k == "pivot_tol") return p->piv_tol;
     if (k == "last_to_host_ms") return p->last_to_host_ms;

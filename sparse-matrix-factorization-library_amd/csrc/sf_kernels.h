@@ -207,6 +207,20 @@ void launch_solve_many_bwd(const SolveTask* t, int nt, int big, const double* Ls
 void launch_solve_many_pack(const double* Bc, int64_t n, int cw, double* X, hipStream_t st);
 void launch_solve_many_unpack(const double* X, int64_t n, int cw, double* Bc, hipStream_t st);
 
+// ---- selected inversion (sf_selinv.hip, sf_chol_plan_selinv) ----
+// one unit: columns [cb, cb + w) of the supernode whose panel starts at lx (factor and arena share the layout), rows at Lsi[rows ..]
+struct SelUnit {
+    int64_t lx, rows;
+    int32_t nsrow, ncol, cb, w;
+    int32_t pair0, npair;       // the supernode's scatter problems (J, a) in the pair table, by first row
+};
+struct SelPair { int64_t map_off; int32_t i; int32_t pad_; };     // problem (J, a): relative map at map_off, J's rows from panel row i
+constexpr int SEL_UW = OUTER_NB;      // unit width of the wide supernodes
+constexpr int SEL_SMALL_W = 64;       // narrow supernodes (one workgroup each): nscol <= SEL_SMALL_W,
+constexpr int SEL_SMALL_M = 512;      // rows below <= SEL_SMALL_M,
+constexpr int SEL_SMALL_Y = 4096;     // (rows below) x nscol <= SEL_SMALL_Y
+constexpr int SEL_MAX_SLABS = 16;     // K slabs of the split products
+
 void launch_noop(hipStream_t st);
 
 // device twin of SparseFrame_validate's residual (C:3182-3263): b_i = 1 + i/n is written to b, r = A x - b, the four maxima

@@ -246,6 +246,28 @@ struct sf_chol_plan {
     double* d_xm = nullptr;
     size_t bytes_solve_many = 0;
     double last_solve_many_ms = 0;
+    // sf_chol_plan_selinv (sf_selinv.hip).  Generations of the factor: factor_gen moves whenever the values or the resident factor
+    // change (set_values, the start of a factorization, an import); fact_gen = factor_gen of the last factorization started,
+    // ok_gen = that of the last one that succeeded (sf_chol_plan_sync) or of an import; sel_gen = factor_gen the arena was computed from
+    int64_t factor_gen = 0, fact_gen = -1, ok_gen = -1, sel_gen = -1;
+    bool fact_done = false;         // the last factorization started has had all its launches enqueued
+    std::vector<int32_t> sel_pair_J, sel_pair_i;    // every scatter problem (J, a) as plan_create enumerated it: J, first panel row,
+    std::vector<int64_t> sel_pair_off;              // relative-map offset (host only)
+    struct SelBig { sf::SelUnit u; int zslabs, sslabs; };
+    struct SelStep { int64_t small_first, small_count, big_first, big_count; };   // one level: big units, then narrow supernodes
+    bool sel_scheduled = false;
+    std::vector<sf::SelUnit> sel_small;
+    std::vector<SelBig> sel_big;
+    std::vector<SelStep> sel_steps;
+    std::vector<sf::SelPair> sel_pairs_h;
+    int64_t sel_linv_elems = 0, sel_y_elems = 0, sel_z_elems = 0, sel_s_elems = 0;
+    double* d_sel = nullptr;            // the arena (xsize doubles), allocated with the scratch by the first call (not in bytes_device)
+    double* d_sel_diag = nullptr;
+    void* d_sel_units = nullptr;
+    void* d_sel_pairs = nullptr;
+    double* d_sel_scratch = nullptr;
+    size_t bytes_selinv = 0;
+    double last_selinv_ms = 0, flops_selinv = 0;
     int device = 0;
     int64_t n = 0, nsuper = 0, nnz = 0, isize = 0, xsize = 0;
     hipStream_t stream = nullptr;
