@@ -224,7 +224,7 @@ def _ok(rc):
 # GEMM: k_gemm modes 0 / 1, k_update_small
 # ---------------------------------------------------------------------------------------------------------------------
 def _gemm_tiles(M, N, K, prob=0, bm=GEMM_BM, bn=GEMM_BM, whole_k=True):
-    """the tiles of the lower trapezoid, as the plan lists them (sf_chol_plan.hip: GEMM and small-update task lists)"""
+    """the tiles of the lower trapezoid, as the plan lists them (sf_plan_build.hip: GEMM and small-update task lists)"""
     nkt = (K + GEMM_BK - 1) // GEMM_BK
     t = [(prob, tm, tn, 0, nkt if whole_k else 0) for tm in range((M + bm - 1) // bm) for tn in range((N + bn - 1) // bn)
          if (tm + 1) * bm - 1 >= tn * bn]
@@ -739,7 +739,7 @@ STEP_PANELS = [(1, 0), (17, 1), (64, 63), (65, 64), (130, 65), (512, 300), (100,
 
 
 def _chol_step_launches(panels, J=0):
-    """the task list of every fused step of the outer block [J, J + 512), one launch per step, as sf_chol_plan.hip builds
+    """the task list of every fused step of the outer block [J, J + 512), one launch per step, as sf_plan_build.hip builds
     them for Cholesky (the block_fused branch of the panel schedule): the diagonal tasks first (their own J = diag, slot =
     index in the launch, a fresh flag each), then the 64-row tiles below each diagonal block, with next_b = the width of
     the future diagonal block of this outer block that the tile's rows are (0: rows below the block's columns)"""
