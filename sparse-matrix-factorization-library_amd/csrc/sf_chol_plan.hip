@@ -15,14 +15,6 @@
 #include "sf_plan_internal.h"
 #include "sf_symbolic.h"
 
-// hipEventElapsedTime whose failure (an event that was never recorded) is expected and must not stay behind as the thread's
-// "last error": callers that poll hipGetLastError after their own launches (PyTorch does) would report it as theirs
-static bool elapsed_ms(float* ms, hipEvent_t a, hipEvent_t b) {
-    if (hipEventElapsedTime(ms, a, b) == hipSuccess) return true;
-    (void)hipGetLastError();
-    return false;
-}
-
 extern "C" {
 
 int sf_device_count(void) {
@@ -1151,10 +1143,6 @@ int sf_lu_plan_sync(sf_lu_plan* p) { return sf_chol_plan_sync(p); }
 int sf_lu_plan_get_factor(sf_lu_plan* p, sf_float* Lsx) { return (p && p->lu) ? sf_chol_plan_get_factor(p, Lsx) : SF_ERR_ARG; }
 double sf_lu_plan_stat(const sf_lu_plan* p, const char* name) { return sf_chol_plan_stat(p, name); }
 int sf_lu_plan_set_profiling(sf_lu_plan* p, int on) { return sf_chol_plan_set_profiling(p, on); }
-int sf_lu_plan_solve(sf_lu_plan* p, const sf_float* b_host, sf_float* x_host) { return (p && p->lu) ? sf_chol_plan_solve(p, b_host, x_host) : SF_ERR_ARG; }
-int sf_lu_plan_solve_many(sf_lu_plan* p, sf_long nrhs, const sf_float* B, sf_long ldb, sf_float* X, sf_long ldx) {
-    return (p && p->lu) ? sf_chol_plan_solve_many(p, nrhs, B, ldb, X, ldx) : SF_ERR_ARG;
-}
 int sf_lu_plan_destroy(sf_lu_plan* p) { return sf_chol_plan_destroy(p); }
 
 void* sf_chol_plan_factor_device_ptr(sf_chol_plan* p) { return p ? (void*)p->d_Lsx : nullptr; }
@@ -1206,170 +1194,6 @@ double sf_chol_plan_stat(const sf_chol_plan* p, const char* name) {
     if (k == "flops_tiles") return p->flops_tiles;
     if (k == "flops_tiles_update") return p->flops_tiles_update;
     return -1;
-}
-
-// x <- (L L^T)^{-1} b (Cholesky, C:3036-3139) or (L U)^{-1} b (LU, L:3592-3700) with the resident factor, permuted
-// space.  LU: unit-lower forward sweep over the L panels, backward sweep over the U^T panels (U x = y <=> (U^T)^T x = y).
-}   // extern "C"
-
-void sf_solve_step_fwd(sf_chol_plan* p, size_t k, const double* base, int* sync, int* tickets, hipStream_t st) {
-    const auto& s = p->solve_steps[k];
-    const int32_t* piv = (p->lu && p->piv_tol > 0.0) ? p->d_piv : nullptr;
-    const int unit = p->lu ? 1 : 0;
-    int* tk = tickets + sf_chol_plan::SOLVE_TICKETS * k;
-    if (s.small) {
-        sf::launch_solve_small_fwd(p->d_solve + s.fwd_first, s.ndiag, base, p->d_Lsi, p->d_x, unit, piv, st);
-    } else {
-        sf::launch_solve_fwd(p->d_solve + s.fwd_first, s.fwd_count, s.big, base, p->d_Lsi, p->d_x, unit, piv, sync, tk, p->d_solve_sync, st);
-    }
-}
-
-void sf_solve_step_bwd(sf_chol_plan* p, size_t k, const double* base, int* sync, int* tickets, hipStream_t st) {
-    const auto& s = p->solve_steps[k];
-    int* tk = tickets + sf_chol_plan::SOLVE_TICKETS * k;
-    if (s.small) {
-        sf::launch_solve_small_bwd(p->d_solve + s.bwd_first, s.ndiag, base, p->d_Lsi, p->d_x, st);
-    } else if (p->solve_bwd_fused) {
-        sf::launch_solve_bwd(p->d_solve + s.bwd_first, s.count, s.big, base, p->d_Lsi, p->d_x, sync, tk + 1, p->d_solve_sync, st, p->d_solveT);
-    } else {
-        sf::launch_solve_bwd(p->d_solve + s.bwd_first, s.nrows_tasks, 0, base, p->d_Lsi, p->d_x, sync, tk + 1, p->d_solve_sync, st);
-        sf::launch_solve_bwd(p->d_solve + s.bwd_first + s.nrows_tasks, s.count - s.nrows_tasks, s.big, base, p->d_Lsi, p->d_x, sync, tk + 2,
-                             p->d_solve_sync, st, p->d_solveT);
-    }
-}
-
-extern "C" {
-
-int sf_chol_plan_solve(sf_chol_plan* p, const sf_float* b_host, sf_float* x_host) {
-    if (!p || !b_host || !x_host) return SF_ERR_ARG;
-    if (p->partial || (p->nsuper > 0 && !p->d_solve)) return SF_ERR_ARG;
-    const double* fwd_base = p->d_Lsx;
-    const double* bwd_base = p->lu ? p->d_Lsx + p->xC : p->d_Lsx;
-    if (p->dry) return SF_ERR_ARG;        // a schedule-only plan has no device side
-    HIP_TRY(hipSetDevice(p->device));
-    hipStream_t st = p->stream;
-    if (p->n <= 0) return SF_OK;
-    HIP_TRY(hipMemcpyAsync(p->d_x, b_host, p->n * sizeof(double), hipMemcpyHostToDevice, st));
-    // the plan's own event pair (ev0/ev1 time the factorization; sf_chol_plan_sync has read them by now): nothing is
-    // created here, so an error return leaks nothing
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    HIP_TRY(hipEventRecord(e0, st));
-    const size_t nst = p->solve_steps.size();
-    int* sync = p->d_solve_sync + 1;
-    int* tickets = sync + p->n_solve_sync;
-    HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, (size_t)(1 + p->n_solve_sync + sf_chol_plan::SOLVE_TICKETS * nst) * sizeof(int), st));
-    for (size_t k = 0; k < nst; ++k) sf_solve_step_fwd(p, k, fwd_base, sync, tickets, st);
-    // (row-major copies of the top steps' diagonal blocks, from the factor as it is now: 117 MB at 128^3, ~0.1 ms)
-    sf::launch_solve_transpose_diag(p->d_solve, p->d_solveT_list, p->n_solveT, bwd_base, p->d_solveT, st);
-    for (size_t k = nst; k-- > 0;) sf_solve_step_bwd(p, k, bwd_base, sync, tickets, st);
-    HIP_TRY(hipEventRecord(e1, st));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(x_host, p->d_x, p->n * sizeof(double), hipMemcpyDeviceToHost, st));
-    int sinfo = 0;
-    HIP_TRY(hipMemcpyAsync(&sinfo, p->d_solve_sync, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (sinfo) return SF_ERR_HIP;       // a bounded in-launch wait ran out (never seen)
-    float ms = 0;
-    if (elapsed_ms(&ms, e0, e1)) p->last_solve_ms = ms;
-    return SF_OK;
-}
-
-}  // extern "C"
-
-// the multi-right-hand-side sweeps: the plan's steps, tasks and sync words, the SVM_W-column kernels on the block d_xm
-static void sf_solve_many_step_fwd(sf_chol_plan* p, size_t k, const double* base, int* sync, int* tickets, hipStream_t st) {
-    const auto& s = p->solve_steps[k];
-    const int32_t* piv = (p->lu && p->piv_tol > 0.0) ? p->d_piv : nullptr;
-    const int unit = p->lu ? 1 : 0;
-    int* tk = tickets + sf_chol_plan::SOLVE_TICKETS * k;
-    if (s.small) {
-        sf::launch_solve_many_small_fwd(p->d_solve + s.fwd_first, s.ndiag, base, p->d_Lsi, p->d_xm, unit, piv, st);
-    } else {
-        sf::launch_solve_many_fwd(p->d_solve + s.fwd_first, s.fwd_count, s.big, base, p->d_Lsi, p->d_xm, unit, piv, sync, tk, p->d_solve_sync, st);
-    }
-}
-
-static void sf_solve_many_step_bwd(sf_chol_plan* p, size_t k, const double* base, int* sync, int* tickets, hipStream_t st) {
-    const auto& s = p->solve_steps[k];
-    int* tk = tickets + sf_chol_plan::SOLVE_TICKETS * k;
-    if (s.small) {
-        sf::launch_solve_many_small_bwd(p->d_solve + s.bwd_first, s.ndiag, base, p->d_Lsi, p->d_xm, st);
-    } else if (p->solve_bwd_fused) {
-        sf::launch_solve_many_bwd(p->d_solve + s.bwd_first, s.count, s.big, base, p->d_Lsi, p->d_xm, sync, tk + 1, p->d_solve_sync, st,
-                                  p->d_solveT);
-    } else {
-        sf::launch_solve_many_bwd(p->d_solve + s.bwd_first, s.nrows_tasks, 0, base, p->d_Lsi, p->d_xm, sync, tk + 1, p->d_solve_sync, st);
-        sf::launch_solve_many_bwd(p->d_solve + s.bwd_first + s.nrows_tasks, s.count - s.nrows_tasks, s.big, base, p->d_Lsi, p->d_xm, sync,
-                                  tk + 2, p->d_solve_sync, st, p->d_solveT);
-    }
-}
-
-extern "C" {
-
-// X <- (L L^T)^{-1} B (LU: (L U)^{-1} B) for nrhs columns, SVM_W of them per forward + backward sweep.  A chunk goes H2D
-// column-major into the staging half of d_xm (one copy when ldb == n, one per column otherwise), a small kernel transposes it
-// into the row-major block the sweep kernels work on (zero columns pad a partial chunk), and the way back is the same in
-// reverse.  Row-major on the device because every row a tile gathers or scatters through Lsi is then one 128-byte run; the
-// transposes run on the device, where they cost two streaming passes over n x SVM_W doubles, instead of as strided host loops
-// or 2-D copies with 8-byte pieces.
-int sf_chol_plan_solve_many(sf_chol_plan* p, sf_long nrhs, const sf_float* B, sf_long ldb, sf_float* X, sf_long ldx) {
-    if (!p || !B || !X || nrhs < 0) return SF_ERR_ARG;
-    if (p->dry || p->partial || p->ooc_groups > 1 || (p->nsuper > 0 && !p->d_solve)) return SF_ERR_ARG;
-    const sf_long ldmin = std::max<sf_long>(p->n, 1);
-    if (ldb < ldmin || ldx < ldmin) return SF_ERR_ARG;
-    if ((const void*)X == (const void*)B && ldx != ldb) return SF_ERR_ARG;
-    if (nrhs == 0 || p->n <= 0) return SF_OK;
-    HIP_TRY(hipSetDevice(p->device));
-    hipStream_t st = p->stream;
-    const int64_t n = p->n;
-    const int W = sf::SVM_W;
-    if (!p->d_xm) {
-        const size_t bytes = 2 * (size_t)n * W * sizeof(double);
-        HIP_TRY(hipMalloc((void**)&p->d_xm, bytes));
-        p->bytes_solve_many = bytes;
-    }
-    double* stage = p->d_xm + (size_t)n * W;
-    const double* fwd_base = p->d_Lsx;
-    const double* bwd_base = p->lu ? p->d_Lsx + p->xC : p->d_Lsx;
-    const size_t nst = p->solve_steps.size();
-    int* sync = p->d_solve_sync + 1;
-    int* tickets = sync + p->n_solve_sync;
-    const size_t sync_bytes = (size_t)(1 + p->n_solve_sync + sf_chol_plan::SOLVE_TICKETS * nst) * sizeof(int);
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    double total_ms = 0;
-    for (sf_long j0 = 0; j0 < nrhs; j0 += W) {
-        const int cw = (int)std::min<sf_long>(W, nrhs - j0);
-        if (ldb == n) {
-            HIP_TRY(hipMemcpyAsync(stage, B + j0 * ldb, (size_t)n * cw * sizeof(double), hipMemcpyHostToDevice, st));
-        } else {
-            for (int c = 0; c < cw; ++c)
-                HIP_TRY(hipMemcpyAsync(stage + (size_t)c * n, B + (j0 + c) * ldb, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-        }
-        HIP_TRY(hipEventRecord(e0, st));
-        sf::launch_solve_many_pack(stage, n, cw, p->d_xm, st);
-        HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, sync_bytes, st));
-        for (size_t k = 0; k < nst; ++k) sf_solve_many_step_fwd(p, k, fwd_base, sync, tickets, st);
-        // (the row-major copies of the top steps' diagonal blocks: once per call)
-        if (j0 == 0) sf::launch_solve_transpose_diag(p->d_solve, p->d_solveT_list, p->n_solveT, bwd_base, p->d_solveT, st);
-        for (size_t k = nst; k-- > 0;) sf_solve_many_step_bwd(p, k, bwd_base, sync, tickets, st);
-        sf::launch_solve_many_unpack(p->d_xm, n, cw, stage, st);
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        if (ldx == n) {
-            HIP_TRY(hipMemcpyAsync(X + j0 * ldx, stage, (size_t)n * cw * sizeof(double), hipMemcpyDeviceToHost, st));
-        } else {
-            for (int c = 0; c < cw; ++c)
-                HIP_TRY(hipMemcpyAsync(X + (j0 + c) * ldx, stage + (size_t)c * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        int sinfo = 0;
-        HIP_TRY(hipMemcpyAsync(&sinfo, p->d_solve_sync, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (sinfo) return SF_ERR_HIP;       // a bounded in-launch wait ran out
-        float ms = 0;
-        if (elapsed_ms(&ms, e0, e1)) total_ms += ms;
-    }
-    p->last_solve_many_ms = total_ms;
-    return SF_OK;
 }
 
 }  // extern "C"

@@ -163,7 +163,7 @@ void launch_gemm(const GemmProb* probs, const GemmTask* tasks, const uint32_t* k
 // Schur updates with K <= SU_MAXK: tasks are SU_TM x SU_TN tiles (GemmTask.tm / .tn in those units), one wave each
 void launch_update_small(const GemmProb* probs, const GemmTask* tasks, int ntasks, double* Lsx, const int32_t* RelMap, hipStream_t st);
 
-// ---- device-side supernodal triangular solves with the resident factor (reference: scalar host loops,
+// ---- device-side supernodal triangular solves with the resident factor (sf_solve.hip; reference: scalar host loops,
 // Cholesky/Source/SparseFrame.c:3074-3134).  SV_B-column steps level by level; one launch per step and direction, the
 // diagonal solve (one workgroup, wave w = 64-column sub-block w) and the SV_ROWS-row tiles hand over inside the launch.
 struct SolveTask {
@@ -182,27 +182,21 @@ struct SolveTask {
 // pivpos != nullptr (LU with pivoting): x_blk is brought into the block's pivot order before the unit-lower solve
 // steps whose panels are all narrow (nscol <= 64): one wave per supernode does its diagonal solve and all its rows, no
 // hand-off; tasks = the step's diagonal tasks only (task.ld = nsrow, task.b = nscol)
-void launch_solve_small_fwd(const SolveTask* t, int nt, const double* Lsx, const int32_t* Lsi, double* x, int unit, const int32_t* pivpos,
-                            hipStream_t st);
-void launch_solve_small_bwd(const SolveTask* t, int nt, const double* Lsx, const int32_t* Lsi, double* x, hipStream_t st);
+// width: 1 = the single-vector kernels on x[n]; SVM_W = the multi-right-hand-side family (sf_chol_plan_solve_many): the same
+// tasks, schedule and sync words, SVM_W right-hand sides per sweep, x an n x SVM_W block stored ROW-major (x[i * SVM_W + c]).
+// 16 = the N of v_mfma_f64_16x16x4f64.
+constexpr int SVM_W = 16;
+void launch_solve_small_fwd(const SolveTask* t, int nt, int width, const double* Lsx, const int32_t* Lsi, double* x, int unit,
+                            const int32_t* pivpos, hipStream_t st);
+void launch_solve_small_bwd(const SolveTask* t, int nt, int width, const double* Lsx, const int32_t* Lsi, double* x, hipStream_t st);
 // big != 0: some panel of the step has more than one 64-column sub-block (the variant with the prefetch registers)
-void launch_solve_fwd(const SolveTask* t, int nt, int big, const double* Lsx, const int32_t* Lsi, double* x, int unit, const int32_t* pivpos,
-                      int* sync, int* ticket, int* info, hipStream_t st);
-void launch_solve_bwd(const SolveTask* t, int nt, int big, const double* Lsx, const int32_t* Lsi, double* x, int* sync, int* ticket, int* info,
-                      hipStream_t st, const double* Tbase = nullptr);
+void launch_solve_fwd(const SolveTask* t, int nt, int width, int big, const double* Lsx, const int32_t* Lsi, double* x, int unit,
+                      const int32_t* pivpos, int* sync, int* ticket, int* info, hipStream_t st);
+void launch_solve_bwd(const SolveTask* t, int nt, int width, int big, const double* Lsx, const int32_t* Lsi, double* x, int* sync, int* ticket,
+                      int* info, hipStream_t st, const double* Tbase = nullptr);
 // row-major copies of the diagonal blocks of the backward diagonal tasks list[0 .. ntasks) (indices into `tasks`) into T
 void launch_solve_transpose_diag(const SolveTask* tasks, const int64_t* list, int64_t ntasks, const double* Lsx, double* T, hipStream_t st);
 
-// ---- multi-right-hand-side twins (sf_chol_plan_solve_many): the same tasks, schedule and sync words, SVM_W right-hand sides per
-// sweep, x an n x SVM_W block stored ROW-major (x[i * SVM_W + c]; see sf_kernels.hip).  16 = the N of v_mfma_f64_16x16x4f64.
-constexpr int SVM_W = 16;
-void launch_solve_many_small_fwd(const SolveTask* t, int nt, const double* Lsx, const int32_t* Lsi, double* x, int unit,
-                                 const int32_t* pivpos, hipStream_t st);
-void launch_solve_many_small_bwd(const SolveTask* t, int nt, const double* Lsx, const int32_t* Lsi, double* x, hipStream_t st);
-void launch_solve_many_fwd(const SolveTask* t, int nt, int big, const double* Lsx, const int32_t* Lsi, double* x, int unit,
-                           const int32_t* pivpos, int* sync, int* ticket, int* info, hipStream_t st);
-void launch_solve_many_bwd(const SolveTask* t, int nt, int big, const double* Lsx, const int32_t* Lsi, double* x, int* sync, int* ticket,
-                           int* info, hipStream_t st, const double* Tbase = nullptr);
 // column-major n x cw (leading dimension n) -> row-major n x SVM_W, columns [cw, SVM_W) zero; and back (columns [0, cw) only)
 void launch_solve_many_pack(const double* Bc, int64_t n, int cw, double* X, hipStream_t st);
 void launch_solve_many_unpack(const double* X, int64_t n, int cw, double* Bc, hipStream_t st);

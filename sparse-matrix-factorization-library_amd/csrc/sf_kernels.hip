@@ -19,7 +19,7 @@
 //                     flag hand-off from the diagonal workgroup to the row workgroups inside the launch
 //   k_build_relmaps : createRelativeMap (CK:42-60), once per plan for every (descendant, ancestor) pair
 //   k_pack_lu       : gathers the device's (L, U^T) panel pairs into the reference's packed LU panels (L:2514-2517)
-//   k_solve_*       : level-scheduled triangular solves with the resident factor (host loops C:3074-3134)
+// (the device solve's kernels, k_solve_*, live in sf_solve.hip)
 //
 // Wavefronts are 64 wide; all tilings below are written for that.
 #include "sf_kernels.h"
@@ -153,12 +153,6 @@ __device__ __forceinline__ double rcp_full(double v) {
     const double c = __builtin_amdgcn_rcp(v);
     const double e = __builtin_fma(-v, c, 1.0);
     return __builtin_fma(c, __builtin_fma(e, e, e), c);
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
 }
 
 // W = the smallest of 8 / 16 / 32 / 64 that holds the block: the elimination is fully unrolled over W columns (registers), and
@@ -571,958 +565,6 @@ k_trsm_block(const TrsmTask* __restrict__ tasks, double* __restrict__ Lsx, const
 void launch_trsm(const TrsmTask* tasks, int ntasks, double* Lsx, const int32_t* pivinv, hipStream_t st) {
     if (ntasks <= 0) return;
     hipLaunchKernelGGL(k_trsm_block, dim3(ntasks), dim3(TRSM_ROWS), 0, st, tasks, Lsx, pivinv);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Triangular solves with the resident factor (L L^T x = b or L U x = b, permuted space; reference: scalar host loops,
-// C:3074-3134, L:3592-3700).  The sweep is a chain of dependent steps, so the step is made BIG and its inside cheap:
-// one launch per (level, 256-column step) and direction (SV_B = 256),
-//   forward : x_blk <- D^{-1} x_blk  (256 x 256 lower-triangular block)  ;  x[rows below] -= L[rows, blk] x_blk
-//   backward: x_blk -= L[rows below, blk]^T x[rows below]               ;  x_blk <- D^{-T} x_blk
-// and both halves hand over INSIDE the launch (tasks claimed by ticket in execution order, producers first in the list).
-// Diagonal task = one workgroup, wave w owns the 64-column sub-block w: its 64 x 64 triangle sits in the lane's registers
-// from the start (all four waves load at once), the off-diagonal 64 x 64 blocks are prefetched one sub-step ahead, the
-// solved sub-vector goes round through LDS: 4 substitution chains of 64 and 3 barriers instead of 4 launches with 4
-// device-scope hand-offs.  No division on the chains (lane j forms 1 / D(j,j) up front).
-// Row tiles = 64 rows x the step's columns: thread (lane, wave) = (row, 64-column chunk) forward, (column, chunk)
-// backward, ALL its 64 matrix entries are in flight before the hand-off, after it 64 FMAs and one atomic.
-// ---------------------------------------------------------------------------------------------------
-constexpr int SV_SPIN_LIMIT = 1 << 22;
-
-__device__ __forceinline__ void sv_publish(int* flag, int value) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ void sv_wait(const int* flag, int value, int* info) {
-    int spins = 0;
-    while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != value) {
-        __builtin_amdgcn_s_sleep(16);       // hundreds of waiting workgroups poll ONE address: keep the L2 channel usable for its writer
-        if (++spins > SV_SPIN_LIMIT) { atomicOr(info, 2); break; }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-template <bool BIG>
-__global__ void __launch_bounds__(256, BIG ? 1 : 2)
-k_solve_fwd(const SolveTask* __restrict__ tasks, const double* __restrict__ Lsx, const int32_t* __restrict__ Lsi,
-            double* __restrict__ x, int unit, const int32_t* __restrict__ pivpos, int* __restrict__ sync, int* __restrict__ ticket,
-            int* __restrict__ info) {
-    __shared__ int s_ticket;
-    __shared__ double xs[SV_B];
-    __shared__ double part[4][NB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_ticket = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const SolveTask t = tasks[__builtin_amdgcn_readfirstlane(s_ticket)];
-    const int b = t.b;                  // <= SV_B columns in this step
-    const int64_t ld = t.ld;
-    const int o = NB * wave;
-    const int bw = min(NB, max(0, b - o));      // this wave's part of the step's columns
-    if (t.nrows == 0) {                 // ---- diagonal task ----
-        const double* P = Lsx + t.panel;
-        double a[NB];       // row `lane` of the sub-block's triangle; unit: the diagonal is implied (LU: the L panel)
-        if (bw > 0) {
-#pragma unroll
-            for (int c = 0; c < NB; ++c) {
-                // unconditional loads from clamped addresses, then select (a load under a per-element condition becomes a
-                // branch plus its own s_waitcnt: 64 dependent round trips)
-                const double v = P[(t.diag + o + min(lane, bw - 1)) + (int64_t)(t.diag + o + min(c, bw - 1)) * ld];
-                a[c] = (lane < bw && c + unit <= lane) ? v : ((c == lane) ? 1.0 : 0.0);
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < NB; ++c) a[c] = (c == lane) ? 1.0 : 0.0;
-        }
-        double* xq = x + t.first_col + t.diag + o;
-        double v = (lane < bw) ? xq[lane] : 0.0;
-        double dinv = 1.0;
-#pragma unroll
-        for (int c = 0; c < NB; ++c) dinv = (c == lane) ? 1.0 / a[c] : dinv;
-        const int nsub = (b + NB - 1) / NB;
-        for (int tt = 0; tt < nsub; ++tt) {
-            const bool below = BIG && wave > tt && bw > 0;
-            double blk[BIG ? NB : 1];       // L(this wave's row, columns of sub-block tt): in flight while wave tt solves
-            if (BIG && below) {
-#pragma unroll
-                for (int k = 0; k < NB; ++k) blk[k] = P[(t.diag + o + min(lane, bw - 1)) + (int64_t)(t.diag + NB * tt + k) * ld];
-            }
-            if (wave == tt) {
-                if (pivpos) {
-                    // LU with pivoting: the row interchanges of this 64-column block, applied as the sweep reaches it
-                    // (LINPACK-style: the L entries to the left of a block were stored at their rows' original places)
-                    const int g0 = t.first_col + t.diag + o;
-                    if (lane < bw) part[0][pivpos[g0 + lane] - g0] = v;
-                    v = (lane < bw) ? part[0][lane] : 0.0;       // one wave: LDS operations complete in order
-                }
-#pragma unroll
-                for (int j = 0; j < NB; ++j) {
-                    const double xj = readlane_f64(v, j) * readlane_f64(dinv, j);
-                    if (lane == j) v = xj;
-                    if (lane > j) v -= a[j] * xj;
-                }
-                xs[o + lane] = (lane < bw) ? v : 0.0;
-            }
-            if (BIG) {
-                __syncthreads();
-                if (below) {
-#pragma unroll
-                    for (int k = 0; k < NB; ++k) v -= blk[k] * xs[NB * tt + k];
-                }
-            }
-        }
-        if (lane < bw) xq[lane] = v;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) sv_publish(sync + t.flag, 1);
-        return;
-    }
-    // ---- row tile: lane = row, wave = 64-column chunk; the 64 entries are in flight while the diagonal block is solved ----
-    // (a "far" tile of a look-ahead step may hold several 64-row groups, t.nrows > 64: one workgroup streams through them -- one
-    // ticket, one task, one flag poll, one load of x_blk for all of them)
-    int nr = min(t.nrows, SV_ROWS);
-    int r = t.row0 + min(lane, nr - 1);
-    double lr[NB];
-    if (bw > 0) {
-        const double* Lr = Lsx + t.panel + r + (int64_t)(t.diag + o) * ld;
-#pragma unroll
-        for (int k = 0; k < NB; ++k) lr[k] = Lr[(int64_t)min(k, bw - 1) * ld];
-    }
-    int32_t gi = Lsi[t.rows + r];
-    if (tid == 0) sv_wait(sync + t.flag, 1, info);
-    __syncthreads();
-    xs[tid] = (tid < b) ? __builtin_nontemporal_load(x + t.first_col + t.diag + tid) : 0.0;
-    __syncthreads();
-    {
-        double acc = 0.0;
-        if (bw > 0) {
-#pragma unroll
-            for (int k = 0; k < NB; ++k) acc += lr[k] * xs[o + k];       // columns beyond b meet xs = 0
-        }
-        part[wave][lane] = acc;
-        __syncthreads();
-        if (wave == 0 && lane < nr) unsafeAtomicAdd(x + gi, -(part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane]));
-    }
-    if (BIG) {          // (only this instantiation walks through further row groups; the plan makes sure of it)
-#pragma unroll 1
-        for (int g0 = SV_ROWS; g0 < t.nrows; g0 += SV_ROWS) {
-            nr = min(t.nrows - g0, SV_ROWS);
-            r = t.row0 + g0 + min(lane, nr - 1);
-            if (bw > 0) {
-                const double* Lr = Lsx + t.panel + r + (int64_t)(t.diag + o) * ld;
-#pragma unroll
-                for (int k = 0; k < NB; ++k) lr[k] = Lr[(int64_t)min(k, bw - 1) * ld];
-            }
-            gi = Lsi[t.rows + r];
-            double acc = 0.0;
-            if (bw > 0) {
-#pragma unroll
-                for (int k = 0; k < NB; ++k) acc += lr[k] * xs[o + k];
-            }
-            __syncthreads();            // part[] of the previous group has been read
-            part[wave][lane] = acc;
-            __syncthreads();
-            if (wave == 0 && lane < nr) unsafeAtomicAdd(x + gi, -(part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane]));
-        }
-    }
-}
-
-template <bool BIG>
-__global__ void __launch_bounds__(256, BIG ? 1 : 2)
-k_solve_bwd(const SolveTask* __restrict__ tasks, const double* __restrict__ Lsx, const int32_t* __restrict__ Lsi,
-            double* __restrict__ x, int* __restrict__ sync, int* __restrict__ ticket, int* __restrict__ info,
-            const double* __restrict__ Tbase) {
-    __shared__ int s_ticket;
-    __shared__ double xs[SV_B];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_ticket = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const SolveTask t = tasks[__builtin_amdgcn_readfirstlane(s_ticket)];
-    const int b = t.b;
-    const int64_t ld = t.ld;
-    const int o = NB * wave;
-    const int bw = min(NB, max(0, b - o));
-    if (t.nrows > 0) {
-        // ---- row tile: lane = row (coalesced loads), wave = 64-column chunk.  p[k] = L(row, column k) x_row has to be summed
-        // over the 64 lanes for every k: a transposing butterfly -- in the step with mask m a lane keeps the half of its
-        // array that matches its bit m and adds the partner's other half -- leaves lane l with the sum of ONE column after
-        // 63 exchanges instead of 64 full reductions.
-        // (a "far" tile of a look-ahead step may hold several 64-row groups, t.nrows > 64: their products are summed in
-        // registers first -- the butterfly is linear -- so the group of tiles costs ONE butterfly and ONE set of atomics on the
-        // 256 words every tile of the step adds to)
-        double p[NB];
-        if (bw > 0) {
-            int nr = min(t.nrows, SV_ROWS);
-            int rr = t.row0 + min(lane, nr - 1);
-            {
-                const double* Lr = Lsx + t.panel + rr + (int64_t)(t.diag + o) * ld;
-#pragma unroll
-                for (int k = 0; k < NB; ++k) p[k] = Lr[(int64_t)min(k, bw - 1) * ld];
-                const double xr = (lane < nr) ? x[Lsi[t.rows + rr]] : 0.0;
-#pragma unroll
-                for (int k = 0; k < NB; ++k) p[k] *= xr;
-            }
-            if (BIG) {
-#pragma unroll 1
-                for (int g0 = SV_ROWS; g0 < t.nrows; g0 += SV_ROWS) {
-                    nr = min(t.nrows - g0, SV_ROWS);
-                    rr = t.row0 + g0 + min(lane, nr - 1);
-                    const double* Lr = Lsx + t.panel + rr + (int64_t)(t.diag + o) * ld;
-                    double q[NB];
-#pragma unroll
-                    for (int k = 0; k < NB; ++k) q[k] = Lr[(int64_t)min(k, bw - 1) * ld];
-                    const double xr = (lane < nr) ? x[Lsi[t.rows + rr]] : 0.0;
-#pragma unroll
-                    for (int k = 0; k < NB; ++k) p[k] += q[k] * xr;
-                }
-            }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const bool up = (lane & m) != 0;
-#pragma unroll
-                for (int i = 0; i < m; ++i) {
-                    const double keep = up ? p[i + m] : p[i];
-                    const double give = up ? p[i] : p[i + m];
-                    p[i] = keep + __shfl_xor(give, m, 64);
-                }
-            }
-            // lane l now holds the column whose index has bit m set exactly where l has it: column l
-            if (lane < bw) unsafeAtomicAdd(x + t.first_col + t.diag + o + lane, -p[0]);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            __hip_atomic_fetch_add(sync + t.flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        return;
-    }
-    // ---- diagonal task: x_blk <- D^{-T} x_blk, sub-blocks from the last to the first; lane = column ----
-    const double* P = Lsx + t.panel;
-    double bcol[NB];    // bcol[c] = D(c, lane): column `lane` of the sub-block's triangle, rows c >= lane (one contiguous run per
-                        // lane: 64 cache lines per load instruction, ~7 us per block -- measured cheaper than coalesced row loads
-                        // plus an in-wave transpose through LDS, which made the backward sweep 23 -> 36 ms)
-    // (steps of the top levels come with a ROW-major copy of their diagonal block, t.tdiag, made at the start of the solve:
-    // D(c, lane) is then one contiguous run across the lanes, i.e. coalesced, for bcol and for blk below)
-    const double* __restrict__ Td = (Tbase && t.tdiag) ? Tbase + (t.tdiag - 1) : nullptr;
-    if (bw > 0) {
-#pragma unroll
-        for (int c = 0; c < NB; ++c) {
-            const double v = Td ? Td[(int64_t)(o + min(c, bw - 1)) * b + (o + min(lane, bw - 1))]
-                                : P[(t.diag + o + min(c, bw - 1)) + (int64_t)(t.diag + o + min(lane, bw - 1)) * ld];
-            bcol[c] = (lane < bw && c < bw && c >= lane) ? v : ((c == lane) ? 1.0 : 0.0);
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < NB; ++c) bcol[c] = (c == lane) ? 1.0 : 0.0;
-    }
-    double dinv = 1.0;
-#pragma unroll
-    for (int c = 0; c < NB; ++c) dinv = (c == lane) ? 1.0 / bcol[c] : dinv;
-    if (t.expect > 0) {
-        if (tid == 0) {
-            int spins = 0;
-            while (__hip_atomic_load(sync + t.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != t.expect) {
-                __builtin_amdgcn_s_sleep(4);
-                if (++spins > SV_SPIN_LIMIT) { atomicOr(info, 2); break; }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();
-    }
-    double* xq = x + t.first_col + t.diag + o;
-    double v = (lane < bw) ? __builtin_nontemporal_load(xq + min(lane, max(bw, 1) - 1)) : 0.0;
-    const int nsub = (b + NB - 1) / NB;
-    for (int tt = nsub - 1; tt >= 0; --tt) {
-        const bool above = BIG && wave < tt && bw > 0;
-        const int bt = min(NB, b - NB * tt);            // rows of sub-block tt
-        double blk[BIG ? NB : 1];                       // L(rows of sub-block tt, this lane's column): one contiguous run
-        if (BIG && above) {
-#pragma unroll
-            for (int k = 0; k < NB; ++k)
-                blk[k] = Td ? Td[(int64_t)(NB * tt + min(k, bt - 1)) * b + (o + min(lane, bw - 1))]
-                            : P[(t.diag + NB * tt + min(k, bt - 1)) + (int64_t)(t.diag + o + min(lane, bw - 1)) * ld];
-        }
-        if (wave == tt) {
-#pragma unroll
-            for (int j = NB - 1; j >= 0; --j) {
-                const double xj = readlane_f64(v, j) * readlane_f64(dinv, j);
-                if (lane == j) v = xj;
-                if (lane < j) v -= bcol[j] * xj;           // D(j, lane) * x_j
-            }
-            xs[o + lane] = (lane < bw) ? v : 0.0;
-        }
-        if (BIG) {
-            __syncthreads();
-            if (above) {
-#pragma unroll
-                for (int k = 0; k < NB; ++k) v -= blk[k] * xs[NB * tt + k];       // rows beyond bt meet xs = 0
-            }
-        }
-    }
-    if (lane < bw) xq[lane] = v;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Steps in which every panel is narrow (nscol <= 64: the swarm levels, tens of thousands of supernodes of a few dozen
-// columns): ONE WAVE per supernode does its whole part of the sweep -- diagonal solve and all its rows -- with no hand-off,
-// four supernodes per workgroup.  (Through the general kernels such a supernode costs a diagonal workgroup plus one workgroup
-// per 64 rows, three of four waves idle in each, and a device-scope hand-off.)  task.ld = nsrow, task.b = nscol.
-// ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256, 2)
-k_solve_small_fwd(const SolveTask* __restrict__ tasks, int ntasks, const double* __restrict__ Lsx, const int32_t* __restrict__ Lsi,
-                  double* __restrict__ x, int unit, const int32_t* __restrict__ pivpos) {
-    __shared__ double ptmp[4][NB];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // the task index is uniform over the wave: say so, or every field of the task (and all address arithmetic) lives in VGPRs
-    const int ti = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
-    if (ti >= ntasks) return;
-    const SolveTask t = tasks[ti];
-    const int b = t.b;
-    const int64_t ld = t.ld;
-    const double* P = Lsx + t.panel;
-    double a[NB];
-#pragma unroll
-    for (int c = 0; c < NB; ++c) {
-        const double v = P[min(lane, b - 1) + (int64_t)min(c, b - 1) * ld];
-        a[c] = (lane < b && c + unit <= lane) ? v : ((c == lane) ? 1.0 : 0.0);
-    }
-    double* xq = x + t.first_col;
-    double v = (lane < b) ? xq[lane] : 0.0;
-    if (pivpos) {
-        if (lane < b) ptmp[wave][pivpos[t.first_col + lane] - t.first_col] = v;
-        v = (lane < b) ? ptmp[wave][lane] : 0.0;
-    }
-    double dinv = 1.0;
-#pragma unroll
-    for (int c = 0; c < NB; ++c) dinv = (c == lane) ? 1.0 / a[c] : dinv;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        const double xj = readlane_f64(v, j) * readlane_f64(dinv, j);
-        if (lane == j) v = xj;
-        if (lane > j) v -= a[j] * xj;
-    }
-    if (lane < b) xq[lane] = v;
-    // the rows below: 64 at a time, lane = row; x_blk[k] is broadcast out of lane k's register
-    for (int r0 = b; r0 < (int)ld; r0 += NB) {
-        const int row = min(r0 + lane, (int)ld - 1);
-#pragma unroll
-        for (int k = 0; k < NB; ++k) a[k] = P[row + (int64_t)min(k, b - 1) * ld];
-        const int32_t gi = Lsi[t.rows + row];
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < NB; ++k) acc += a[k] * readlane_f64(v, k);       // lanes >= b hold v = 0
-        if (r0 + lane < (int)ld) unsafeAtomicAdd(x + gi, -acc);
-    }
-}
-
-__global__ void __launch_bounds__(256, 2)
-k_solve_small_bwd(const SolveTask* __restrict__ tasks, int ntasks, const double* __restrict__ Lsx, const int32_t* __restrict__ Lsi,
-                  double* __restrict__ x) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ti = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
-    if (ti >= ntasks) return;
-    const SolveTask t = tasks[ti];
-    const int b = t.b;
-    const int64_t ld = t.ld;
-    const double* P = Lsx + t.panel;
-    // s_c = sum over the rows below of L(row, c) x[row]: lane = row (coalesced), then the transposing butterfly
-    double s = 0.0;
-    double p[NB];
-    for (int r0 = b; r0 < (int)ld; r0 += NB) {
-        const int row = min(r0 + lane, (int)ld - 1);
-#pragma unroll
-        for (int k = 0; k < NB; ++k) p[k] = P[row + (int64_t)min(k, b - 1) * ld];
-        const double xr = (r0 + lane < (int)ld) ? x[Lsi[t.rows + row]] : 0.0;
-#pragma unroll
-        for (int k = 0; k < NB; ++k) p[k] *= xr;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            const bool up = (lane & m) != 0;
-#pragma unroll
-            for (int i = 0; i < m; ++i) {
-                const double keep = up ? p[i + m] : p[i];
-                const double give = up ? p[i] : p[i + m];
-                p[i] = keep + __shfl_xor(give, m, 64);
-            }
-        }
-        s += p[0];
-    }
-    // D^T x_blk = x_blk - s, lane = column
-#pragma unroll
-    for (int c = 0; c < NB; ++c) {
-        const double v = P[min(c, b - 1) + (int64_t)min(lane, b - 1) * ld];
-        p[c] = (lane < b && c < b && c >= lane) ? v : ((c == lane) ? 1.0 : 0.0);
-    }
-    double dinv = 1.0;
-#pragma unroll
-    for (int c = 0; c < NB; ++c) dinv = (c == lane) ? 1.0 / p[c] : dinv;
-    double* xq = x + t.first_col;
-    double v = (lane < b) ? xq[lane] - s : 0.0;
-#pragma unroll
-    for (int j = NB - 1; j >= 0; --j) {
-        const double xj = readlane_f64(v, j) * readlane_f64(dinv, j);
-        if (lane == j) v = xj;
-        if (lane < j) v -= p[j] * xj;
-    }
-    if (lane < b) xq[lane] = v;
-}
-
-void launch_solve_small_fwd(const SolveTask* t, int nt, const double* Lsx, const int32_t* Lsi, double* x, int unit, const int32_t* pivpos,
-                            hipStream_t st) {
-    if (nt > 0) hipLaunchKernelGGL(k_solve_small_fwd, dim3((nt + 3) / 4), dim3(256), 0, st, t, nt, Lsx, Lsi, x, unit, pivpos);
-}
-void launch_solve_small_bwd(const SolveTask* t, int nt, const double* Lsx, const int32_t* Lsi, double* x, hipStream_t st) {
-    if (nt > 0) hipLaunchKernelGGL(k_solve_small_bwd, dim3((nt + 3) / 4), dim3(256), 0, st, t, nt, Lsx, Lsi, x);
-}
-
-void launch_solve_fwd(const SolveTask* t, int nt, int big, const double* Lsx, const int32_t* Lsi, double* x, int unit, const int32_t* pivpos,
-                      int* sync, int* ticket, int* info, hipStream_t st) {
-    if (nt <= 0) return;
-    if (big) hipLaunchKernelGGL(k_solve_fwd<true>, dim3(nt), dim3(256), 0, st, t, Lsx, Lsi, x, unit, pivpos, sync, ticket, info);
-    else hipLaunchKernelGGL(k_solve_fwd<false>, dim3(nt), dim3(256), 0, st, t, Lsx, Lsi, x, unit, pivpos, sync, ticket, info);
-}
-void launch_solve_bwd(const SolveTask* t, int nt, int big, const double* Lsx, const int32_t* Lsi, double* x, int* sync, int* ticket, int* info,
-                      hipStream_t st, const double* Tbase) {
-    if (nt <= 0) return;
-    if (big) hipLaunchKernelGGL(k_solve_bwd<true>, dim3(nt), dim3(256), 0, st, t, Lsx, Lsi, x, sync, ticket, info, Tbase);
-    else hipLaunchKernelGGL(k_solve_bwd<false>, dim3(nt), dim3(256), 0, st, t, Lsx, Lsi, x, sync, ticket, info, Tbase);
-}
-
-// T(r, c) = D(r, c), row-major b x b, for the lower triangle's 64 x 64 tiles of a step's diagonal block (one workgroup per tile,
-// transposed through LDS: reads run down the panel's columns, writes along the copy's rows)
-__global__ void __launch_bounds__(256)
-k_solve_transpose_diag(const SolveTask* __restrict__ tasks, const int64_t* __restrict__ list, const double* __restrict__ Lsx,
-                       double* __restrict__ T) {
-    __shared__ double tile[64][65];
-    const SolveTask t = tasks[list[blockIdx.x >> 4]];
-    const int ti = (blockIdx.x & 15) >> 2, tj = blockIdx.x & 3, b = t.b;
-    if (tj > ti || 64 * ti >= b || 64 * tj >= b || !t.tdiag) return;
-    const double* __restrict__ P = Lsx + t.panel;
-    double* __restrict__ Td = T + (t.tdiag - 1);
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    for (int cc = ty; cc < 64; cc += 4) {
-        const int r = 64 * ti + tx, c = 64 * tj + cc;
-        if (r < b && c < b) tile[cc][tx] = P[(t.diag + r) + (int64_t)(t.diag + c) * t.ld];
-    }
-    __syncthreads();
-    for (int rr = ty; rr < 64; rr += 4) {
-        const int r = 64 * ti + rr, c = 64 * tj + tx;
-        if (r < b && c < b) Td[(int64_t)r * b + c] = tile[tx][rr];
-    }
-}
-
-void launch_solve_transpose_diag(const SolveTask* tasks, const int64_t* list, int64_t ntasks, const double* Lsx, double* T, hipStream_t st) {
-    if (ntasks <= 0) return;
-    hipLaunchKernelGGL(k_solve_transpose_diag, dim3((unsigned)(ntasks * 16)), dim3(256), 0, st, tasks, list, Lsx, T);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Multi-right-hand-side twins of the solve kernels (sf_chol_plan_solve_many): the same tasks, schedule, sync words, tickets
-// and look-ahead order, SVM_W right-hand sides carried through one sweep, so the factor is read once for all of them.
-// x is an n x SVM_W block stored ROW-major, x[i * SVM_W + c]: the row a tile gathers or scatters through Lsi is one contiguous
-// run of SVM_W doubles (128 bytes), and x_blk of a step is one contiguous run of b rows.  Every operation acts on each column
-// on its own (no value of one right-hand side ever meets another's), so a NaN / Inf stays in its column.
-//   diagonal tasks: the twins' substitution chains; the SVM_W values of a lane's row live in LDS and go through the chain
-//                   SVM_CW columns per pass (a runtime loop: the registers stay statically indexed, nothing spills)
-//   forward tile  : lane = row, wave = 64-column chunk, x_blk (b x SVM_W) staged in LDS and read by broadcast; the 4 waves'
-//                   partial products meet in LDS and go out as SVM_W atomics per row, consecutive threads on consecutive words
-//   backward tile : lane = COLUMN (its 64 entries one contiguous run down the panel column), the tile's x rows staged in LDS:
-//                   a (b x 64) x (64 x SVM_W) product -- the twins' transposing butterfly would need 64 * SVM_W registers
-// LDS rows are padded to SVM_LD doubles (144 bytes: 16-byte aligned, staggered across the banks).
-// ---------------------------------------------------------------------------------------------------
-constexpr int SVM_LD = SVM_W + 2;
-constexpr int SVM_CW = 4;
-
-// forward substitution of a 64 x 64 lower-triangular block on the SVM_W columns of the wave's rows (xrow = this lane's row)
-__device__ __forceinline__ void svm_chain_fwd(const double (&a)[NB], double dinv, double* xrow, int lane) {
-#pragma unroll 1
-    for (int cg = 0; cg < SVM_W; cg += SVM_CW) {
-        double v[SVM_CW];
-#pragma unroll
-        for (int c = 0; c < SVM_CW; ++c) v[c] = xrow[cg + c];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const double dj = readlane_f64(dinv, j);
-#pragma unroll
-            for (int c = 0; c < SVM_CW; ++c) {
-                const double xj = readlane_f64(v[c], j) * dj;
-                if (lane == j) v[c] = xj;
-                if (lane > j) v[c] -= a[j] * xj;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < SVM_CW; ++c) xrow[cg + c] = v[c];
-    }
-}
-
-// backward substitution with the transpose: bcol[j] = D(j, lane)
-__device__ __forceinline__ void svm_chain_bwd(const double (&bcol)[NB], double dinv, double* xrow, int lane) {
-#pragma unroll 1
-    for (int cg = 0; cg < SVM_W; cg += SVM_CW) {
-        double v[SVM_CW];
-#pragma unroll
-        for (int c = 0; c < SVM_CW; ++c) v[c] = xrow[cg + c];
-#pragma unroll
-        for (int j = NB - 1; j >= 0; --j) {
-            const double dj = readlane_f64(dinv, j);
-#pragma unroll
-            for (int c = 0; c < SVM_CW; ++c) {
-                const double xj = readlane_f64(v[c], j) * dj;
-                if (lane == j) v[c] = xj;
-                if (lane < j) v[c] -= bcol[j] * xj;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < SVM_CW; ++c) xrow[cg + c] = v[c];
-    }
-}
-
-// xrow[c] -= sum_k w[k] S[k][c] (S in LDS, rows SVM_LD apart, read by broadcast)
-__device__ __forceinline__ void svm_sub_product(const double (&w)[NB], const double* S, double* xrow) {
-#pragma unroll 1
-    for (int cg = 0; cg < SVM_W; cg += SVM_CW) {
-        double acc[SVM_CW];
-#pragma unroll
-        for (int c = 0; c < SVM_CW; ++c) acc[c] = 0.0;
-#pragma unroll
-        for (int k = 0; k < NB; ++k)
-#pragma unroll
-            for (int c = 0; c < SVM_CW; ++c) acc[c] += w[k] * S[k * SVM_LD + cg + c];
-#pragma unroll
-        for (int c = 0; c < SVM_CW; ++c) xrow[cg + c] -= acc[c];
-    }
-}
-
-// out[c] = sum_k w[k] S[k][c]
-__device__ __forceinline__ void svm_product(const double (&w)[NB], const double* S, double* out) {
-#pragma unroll 1
-    for (int cg = 0; cg < SVM_W; cg += SVM_CW) {
-        double acc[SVM_CW];
-#pragma unroll
-        for (int c = 0; c < SVM_CW; ++c) acc[c] = 0.0;
-#pragma unroll
-        for (int k = 0; k < NB; ++k)
-#pragma unroll
-            for (int c = 0; c < SVM_CW; ++c) acc[c] += w[k] * S[k * SVM_LD + cg + c];
-#pragma unroll
-        for (int c = 0; c < SVM_CW; ++c) out[cg + c] = acc[c];
-    }
-}
-
-template <bool BIG>
-__global__ void __launch_bounds__(256, BIG ? 1 : 2)
-k_solve_many_fwd(const SolveTask* __restrict__ tasks, const double* __restrict__ Lsx, const int32_t* __restrict__ Lsi,
-                 double* __restrict__ x, int unit, const int32_t* __restrict__ pivpos, int* __restrict__ sync, int* __restrict__ ticket,
-                 int* __restrict__ info) {
-    __shared__ int s_ticket;
-    __shared__ int32_t s_gi[SV_ROWS];
-    __shared__ double xs[SV_B * SVM_LD];
-    __shared__ double part[4 * NB * SVM_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_ticket = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const SolveTask t = tasks[__builtin_amdgcn_readfirstlane(s_ticket)];
-    const int b = t.b;
-    const int64_t ld = t.ld;
-    const int o = NB * wave;
-    const int bw = min(NB, max(0, b - o));
-    if (t.nrows == 0) {                 // ---- diagonal task (k_solve_fwd's; x_blk in LDS, row o + lane = this lane's) ----
-        const double* P = Lsx + t.panel;
-        double a[NB];
-        if (bw > 0) {
-#pragma unroll
-            for (int c = 0; c < NB; ++c) {
-                const double v = P[(t.diag + o + min(lane, bw - 1)) + (int64_t)(t.diag + o + min(c, bw - 1)) * ld];
-                a[c] = (lane < bw && c + unit <= lane) ? v : ((c == lane) ? 1.0 : 0.0);
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < NB; ++c) a[c] = (c == lane) ? 1.0 : 0.0;
-        }
-        double* xq = x + (int64_t)(t.first_col + t.diag + o) * SVM_W;
-        double* xrow = xs + (o + lane) * SVM_LD;
-        if (bw > 0) {
-            const double* src = xq + (int64_t)min(lane, bw - 1) * SVM_W;
-#pragma unroll
-            for (int c = 0; c < SVM_W; ++c) xrow[c] = (lane < bw) ? src[c] : 0.0;
-        } else {
-#pragma unroll
-            for (int c = 0; c < SVM_W; ++c) xrow[c] = 0.0;
-        }
-        double dinv = 1.0;
-#pragma unroll
-        for (int c = 0; c < NB; ++c) dinv = (c == lane) ? 1.0 / a[c] : dinv;
-        const int nsub = (b + NB - 1) / NB;
-        for (int tt = 0; tt < nsub; ++tt) {
-            const bool below = BIG && wave > tt && bw > 0;
-            double blk[NB];            // (read only when BIG)
-            if (BIG && below) {
-#pragma unroll
-                for (int k = 0; k < NB; ++k) blk[k] = P[(t.diag + o + min(lane, bw - 1)) + (int64_t)(t.diag + NB * tt + k) * ld];
-            }
-            if (wave == tt) {
-                if (pivpos) {
-                    // the block's row interchanges, every column alike (through this wave's own part of `part`; one wave: LDS in order)
-                    double* pw = part + wave * NB * SVM_LD;
-                    const int g0 = t.first_col + t.diag + o;
-                    if (lane < bw) {
-                        const int q = pivpos[g0 + lane] - g0;
-#pragma unroll
-                        for (int c = 0; c < SVM_W; ++c) pw[q * SVM_LD + c] = xrow[c];
-                    }
-#pragma unroll
-                    for (int c = 0; c < SVM_W; ++c) xrow[c] = (lane < bw) ? pw[lane * SVM_LD + c] : 0.0;
-                }
-                svm_chain_fwd(a, dinv, xrow, lane);
-                if (lane >= bw) {
-#pragma unroll
-                    for (int c = 0; c < SVM_W; ++c) xrow[c] = 0.0;
-                }
-            }
-            if (BIG) {
-                __syncthreads();
-                if (below) {
-                    double* blkS = xs + NB * tt * SVM_LD;
-                    svm_sub_product(blk, blkS, xrow);       // rows beyond b of sub-block tt hold 0
-                }
-            }
-        }
-        if (lane < bw) {
-#pragma unroll
-            for (int c = 0; c < SVM_W; ++c) xq[(int64_t)lane * SVM_W + c] = xrow[c];
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) sv_publish(sync + t.flag, 1);
-        return;
-    }
-    // ---- row tile: lane = row, wave = 64-column chunk ----
-    int nr = min(t.nrows, SV_ROWS);
-    int r = t.row0 + min(lane, nr - 1);
-    double lr[NB];
-    if (bw > 0) {
-        const double* Lr = Lsx + t.panel + r + (int64_t)(t.diag + o) * ld;
-#pragma unroll
-        for (int k = 0; k < NB; ++k) lr[k] = Lr[(int64_t)min(k, bw - 1) * ld];
-    }
-    if (wave == 0) s_gi[lane] = Lsi[t.rows + r];
-    if (tid == 0) sv_wait(sync + t.flag, 1, info);
-    __syncthreads();
-    {
-        const double* xb = x + (int64_t)(t.first_col + t.diag) * SVM_W;
-        for (int e = tid; e < SV_B * SVM_W; e += 256) {
-            const int rr = e / SVM_W, c = e % SVM_W;
-            xs[rr * SVM_LD + c] = (rr < b) ? __builtin_nontemporal_load(xb + e) : 0.0;
-        }
-    }
-    __syncthreads();
-    double* prow = part + (wave * NB + lane) * SVM_LD;
-    for (int g0 = 0;;) {
-        if (bw > 0) svm_product(lr, xs + o * SVM_LD, prow);      // columns beyond b meet xs = 0
-        else {
-#pragma unroll
-            for (int c = 0; c < SVM_W; ++c) prow[c] = 0.0;
-        }
-        __syncthreads();
-        for (int e = tid; e < SV_ROWS * SVM_W; e += 256) {
-            const int rr = e / SVM_W, c = e % SVM_W;
-            if (rr < nr)
-                unsafeAtomicAdd(x + (int64_t)s_gi[rr] * SVM_W + c,
-                                -(part[rr * SVM_LD + c] + part[(NB + rr) * SVM_LD + c] + part[(2 * NB + rr) * SVM_LD + c] +
-                                  part[(3 * NB + rr) * SVM_LD + c]));
-        }
-        g0 += SV_ROWS;
-        if (!BIG || g0 >= t.nrows) break;
-        // (a far tile of several 64-row groups: the next group; x_blk stays in LDS)
-        nr = min(t.nrows - g0, SV_ROWS);
-        r = t.row0 + g0 + min(lane, nr - 1);
-        if (bw > 0) {
-            const double* Lr = Lsx + t.panel + r + (int64_t)(t.diag + o) * ld;
-#pragma unroll
-            for (int k = 0; k < NB; ++k) lr[k] = Lr[(int64_t)min(k, bw - 1) * ld];
-        }
-        const int32_t gi = Lsi[t.rows + r];
-        __syncthreads();                // part[] and s_gi[] of the previous group have been read
-        if (wave == 0) s_gi[lane] = gi;
-    }
-}
-
-// (one workgroup per CU as the register bound: at two, the BIG = false instantiation spills)
-template <bool BIG>
-__global__ void __launch_bounds__(256, 1)
-k_solve_many_bwd(const SolveTask* __restrict__ tasks, const double* __restrict__ Lsx, const int32_t* __restrict__ Lsi,
-                 double* __restrict__ x, int* __restrict__ sync, int* __restrict__ ticket, int* __restrict__ info,
-                 const double* __restrict__ Tbase) {
-    __shared__ int s_ticket;
-    __shared__ double xs[SV_B * SVM_LD];      // diagonal task: x_blk; row tile: the tile's x rows (SV_ROWS x SVM_W)
-    __shared__ double acc_s[4 * NB * SVM_LD];  // row tile: the products, lane = column
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_ticket = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const SolveTask t = tasks[__builtin_amdgcn_readfirstlane(s_ticket)];
-    const int b = t.b;
-    const int64_t ld = t.ld;
-    const int o = NB * wave;
-    const int bw = min(NB, max(0, b - o));
-    if (t.nrows > 0) {
-        // ---- row tile: x_blk[column, :] -= sum over the rows of L(row, column) x[row, :]; lane = column, wave = 64-column chunk
-        double* arow = acc_s + (wave * NB + lane) * SVM_LD;        // -(the sum so far)
-#pragma unroll
-        for (int c = 0; c < SVM_W; ++c) arow[c] = 0.0;
-        for (int g0 = 0;;) {
-            const int nr = min(t.nrows - g0, SV_ROWS);
-            double lc[NB];
-            if (bw > 0) {
-                const double* Lc = Lsx + t.panel + (t.row0 + g0) + (int64_t)(t.diag + o + min(lane, bw - 1)) * ld;
-#pragma unroll
-                for (int k = 0; k < NB; ++k) lc[k] = Lc[min(k, nr - 1)];
-            }
-            if (g0 > 0) __syncthreads();        // xs of the previous group has been read
-            for (int e = tid; e < SV_ROWS * SVM_W; e += 256) {
-                const int rr = e / SVM_W, c = e % SVM_W;
-                xs[rr * SVM_LD + c] = (rr < nr) ? x[(int64_t)Lsi[t.rows + t.row0 + g0 + min(rr, nr - 1)] * SVM_W + c] : 0.0;
-            }
-            __syncthreads();
-            if (bw > 0) svm_sub_product(lc, xs, arow);          // rows beyond nr meet xs = 0
-            g0 += SV_ROWS;
-            if (!BIG || g0 >= t.nrows) break;
-        }
-        if (lane < bw) {
-            double* xc = x + (int64_t)(t.first_col + t.diag + o + lane) * SVM_W;
-#pragma unroll
-            for (int c = 0; c < SVM_W; ++c) unsafeAtomicAdd(xc + c, arow[c]);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            __hip_atomic_fetch_add(sync + t.flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        return;
-    }
-    // ---- diagonal task (k_solve_bwd's; x_blk in LDS, row o + lane = this lane's; lane = column of the block) ----
-    const double* P = Lsx + t.panel;
-    double bcol[NB];
-    const double* __restrict__ Td = (Tbase && t.tdiag) ? Tbase + (t.tdiag - 1) : nullptr;
-    if (bw > 0) {
-#pragma unroll
-        for (int c = 0; c < NB; ++c) {
-            const double v = Td ? Td[(int64_t)(o + min(c, bw - 1)) * b + (o + min(lane, bw - 1))]
-                                : P[(t.diag + o + min(c, bw - 1)) + (int64_t)(t.diag + o + min(lane, bw - 1)) * ld];
-            bcol[c] = (lane < bw && c < bw && c >= lane) ? v : ((c == lane) ? 1.0 : 0.0);
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < NB; ++c) bcol[c] = (c == lane) ? 1.0 : 0.0;
-    }
-    double dinv = 1.0;
-#pragma unroll
-    for (int c = 0; c < NB; ++c) dinv = (c == lane) ? 1.0 / bcol[c] : dinv;
-    if (t.expect > 0) {
-        if (tid == 0) {
-            int spins = 0;
-            while (__hip_atomic_load(sync + t.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != t.expect) {
-                __builtin_amdgcn_s_sleep(4);
-                if (++spins > SV_SPIN_LIMIT) { atomicOr(info, 2); break; }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();
-    }
-    double* xq = x + (int64_t)(t.first_col + t.diag + o) * SVM_W;
-    double* xrow = xs + (o + lane) * SVM_LD;
-    if (bw > 0) {
-        const double* src = xq + (int64_t)min(lane, bw - 1) * SVM_W;
-#pragma unroll
-        for (int c = 0; c < SVM_W; ++c) xrow[c] = (lane < bw) ? __builtin_nontemporal_load(src + c) : 0.0;
-    } else {
-#pragma unroll
-        for (int c = 0; c < SVM_W; ++c) xrow[c] = 0.0;
-    }
-    const int nsub = (b + NB - 1) / NB;
-    for (int tt = nsub - 1; tt >= 0; --tt) {
-        const bool above = BIG && wave < tt && bw > 0;
-        const int bt = min(NB, b - NB * tt);
-        double blk[NB];            // (read only when BIG)
-        if (BIG && above) {
-#pragma unroll
-            for (int k = 0; k < NB; ++k)
-                blk[k] = Td ? Td[(int64_t)(NB * tt + min(k, bt - 1)) * b + (o + min(lane, bw - 1))]
-                            : P[(t.diag + NB * tt + min(k, bt - 1)) + (int64_t)(t.diag + o + min(lane, bw - 1)) * ld];
-        }
-        if (wave == tt) {
-            svm_chain_bwd(bcol, dinv, xrow, lane);
-            if (lane >= bw) {
-#pragma unroll
-                for (int c = 0; c < SVM_W; ++c) xrow[c] = 0.0;
-            }
-        }
-        if (BIG) {
-            __syncthreads();
-            if (above) svm_sub_product(blk, xs + NB * tt * SVM_LD, xrow);     // rows beyond bt hold 0
-        }
-    }
-    if (lane < bw) {
-#pragma unroll
-        for (int c = 0; c < SVM_W; ++c) xq[(int64_t)lane * SVM_W + c] = xrow[c];
-    }
-}
-
-// one wave per narrow supernode (k_solve_small_*), x_blk in this wave's part of LDS
-__global__ void __launch_bounds__(256, 2)
-k_solve_many_small_fwd(const SolveTask* __restrict__ tasks, int ntasks, const double* __restrict__ Lsx, const int32_t* __restrict__ Lsi,
-                       double* __restrict__ x, int unit, const int32_t* __restrict__ pivpos) {
-    __shared__ double xs[4 * NB * SVM_LD];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ti = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
-    if (ti >= ntasks) return;
-    const SolveTask t = tasks[ti];
-    const int b = t.b;
-    const int64_t ld = t.ld;
-    const double* P = Lsx + t.panel;
-    double* xw = xs + wave * NB * SVM_LD;
-    double* xrow = xw + lane * SVM_LD;
-    double a[NB];
-#pragma unroll
-    for (int c = 0; c < NB; ++c) {
-        const double v = P[min(lane, b - 1) + (int64_t)min(c, b - 1) * ld];
-        a[c] = (lane < b && c + unit <= lane) ? v : ((c == lane) ? 1.0 : 0.0);
-    }
-    double* xq = x + (int64_t)t.first_col * SVM_W;
-    {
-        const double* src = xq + (int64_t)min(lane, b - 1) * SVM_W;
-        // pivoting: row lane of x_blk goes to the row its interchanges gave it (rows >= b: zero, nothing moves there)
-        const int q = (pivpos && lane < b) ? pivpos[t.first_col + lane] - t.first_col : lane;
-#pragma unroll
-        for (int c = 0; c < SVM_W; ++c) xw[q * SVM_LD + c] = (lane < b) ? src[c] : 0.0;
-    }
-    double dinv = 1.0;
-#pragma unroll
-    for (int c = 0; c < NB; ++c) dinv = (c == lane) ? 1.0 / a[c] : dinv;
-    svm_chain_fwd(a, dinv, xrow, lane);
-    if (lane < b) {
-#pragma unroll
-        for (int c = 0; c < SVM_W; ++c) xq[(int64_t)lane * SVM_W + c] = xrow[c];
-    } else {
-#pragma unroll
-        for (int c = 0; c < SVM_W; ++c) xrow[c] = 0.0;
-    }
-    // the rows below: 64 at a time, lane = row; x_blk read by broadcast out of LDS
-    double acc[SVM_W];
-    for (int r0 = b; r0 < (int)ld; r0 += NB) {
-        const int row = min(r0 + lane, (int)ld - 1);
-#pragma unroll
-        for (int k = 0; k < NB; ++k) a[k] = P[row + (int64_t)min(k, b - 1) * ld];
-        const int32_t gi = Lsi[t.rows + row];
-        svm_product(a, xw, acc);                   // rows >= b of xw hold 0
-        if (r0 + lane < (int)ld) {
-            double* xg = x + (int64_t)gi * SVM_W;
-#pragma unroll
-            for (int c = 0; c < SVM_W; ++c) unsafeAtomicAdd(xg + c, -acc[c]);
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256, 2)
-k_solve_many_small_bwd(const SolveTask* __restrict__ tasks, int ntasks, const double* __restrict__ Lsx, const int32_t* __restrict__ Lsi,
-                       double* __restrict__ x) {
-    __shared__ double xs[4 * NB * SVM_LD];     // the 64 rows' x being summed
-    __shared__ double vs[4 * NB * SVM_LD];     // x_blk, row lane = this lane's
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ti = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
-    if (ti >= ntasks) return;
-    const SolveTask t = tasks[ti];
-    const int b = t.b;
-    const int64_t ld = t.ld;
-    const double* P = Lsx + t.panel;
-    double* xw = xs + wave * NB * SVM_LD;
-    double* xrow = vs + (wave * NB + lane) * SVM_LD;
-    double* xq = x + (int64_t)t.first_col * SVM_W;
-    {
-        const double* src = xq + (int64_t)min(lane, b - 1) * SVM_W;
-#pragma unroll
-        for (int c = 0; c < SVM_W; ++c) xrow[c] = (lane < b) ? src[c] : 0.0;
-    }
-    // x_blk[lane, :] -= sum over the rows below of L(row, lane) x[row, :]: lane = column, the 64 rows' x in LDS
-    double p[NB];
-    for (int r0 = b; r0 < (int)ld; r0 += NB) {
-#pragma unroll
-        for (int k = 0; k < NB; ++k) p[k] = P[min(r0 + k, (int)ld - 1) + (int64_t)min(lane, b - 1) * ld];
-        const int row = min(r0 + lane, (int)ld - 1);
-        const double* xr = x + (int64_t)Lsi[t.rows + row] * SVM_W;
-        const bool live = r0 + lane < (int)ld;
-#pragma unroll
-        for (int c = 0; c < SVM_W; ++c) xw[lane * SVM_LD + c] = live ? xr[c] : 0.0;
-        svm_sub_product(p, xw, xrow);              // rows beyond ld meet xw = 0
-    }
-    // D^T x_blk = x_blk - s, lane = column
-#pragma unroll
-    for (int c = 0; c < NB; ++c) {
-        const double v = P[min(c, b - 1) + (int64_t)min(lane, b - 1) * ld];
-        p[c] = (lane < b && c < b && c >= lane) ? v : ((c == lane) ? 1.0 : 0.0);
-    }
-    double dinv = 1.0;
-#pragma unroll
-    for (int c = 0; c < NB; ++c) dinv = (c == lane) ? 1.0 / p[c] : dinv;
-    svm_chain_bwd(p, dinv, xrow, lane);
-    if (lane < b) {
-#pragma unroll
-        for (int c = 0; c < SVM_W; ++c) xq[(int64_t)lane * SVM_W + c] = xrow[c];
-    }
-}
-
-// column-major n x cw (leading dimension n) <-> the row-major n x SVM_W block; pack zero-fills the columns [cw, SVM_W).
-// Thread e = (column e / n, row e % n): the column-major side is read / written in coalesced runs.
-__global__ void __launch_bounds__(256)
-k_solve_many_pack(const double* __restrict__ Bc, int64_t n, int cw, double* __restrict__ X) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= n * SVM_W) return;
-    const int64_t i = e % n;
-    const int c = (int)(e / n);
-    X[i * SVM_W + c] = (c < cw) ? Bc[i + (int64_t)c * n] : 0.0;
-}
-
-__global__ void __launch_bounds__(256)
-k_solve_many_unpack(const double* __restrict__ X, int64_t n, int cw, double* __restrict__ Bc) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= n * cw) return;
-    const int64_t i = e % n;
-    const int c = (int)(e / n);
-    Bc[i + (int64_t)c * n] = X[i * SVM_W + c];
-}
-
-void launch_solve_many_small_fwd(const SolveTask* t, int nt, const double* Lsx, const int32_t* Lsi, double* x, int unit,
-                                 const int32_t* pivpos, hipStream_t st) {
-    if (nt > 0) hipLaunchKernelGGL(k_solve_many_small_fwd, dim3((nt + 3) / 4), dim3(256), 0, st, t, nt, Lsx, Lsi, x, unit, pivpos);
-}
-void launch_solve_many_small_bwd(const SolveTask* t, int nt, const double* Lsx, const int32_t* Lsi, double* x, hipStream_t st) {
-    if (nt > 0) hipLaunchKernelGGL(k_solve_many_small_bwd, dim3((nt + 3) / 4), dim3(256), 0, st, t, nt, Lsx, Lsi, x);
-}
-void launch_solve_many_fwd(const SolveTask* t, int nt, int big, const double* Lsx, const int32_t* Lsi, double* x, int unit,
-                           const int32_t* pivpos, int* sync, int* ticket, int* info, hipStream_t st) {
-    if (nt <= 0) return;
-    if (big) hipLaunchKernelGGL(k_solve_many_fwd<true>, dim3(nt), dim3(256), 0, st, t, Lsx, Lsi, x, unit, pivpos, sync, ticket, info);
-    else hipLaunchKernelGGL(k_solve_many_fwd<false>, dim3(nt), dim3(256), 0, st, t, Lsx, Lsi, x, unit, pivpos, sync, ticket, info);
-}
-void launch_solve_many_bwd(const SolveTask* t, int nt, int big, const double* Lsx, const int32_t* Lsi, double* x, int* sync, int* ticket,
-                           int* info, hipStream_t st, const double* Tbase) {
-    if (nt <= 0) return;
-    if (big) hipLaunchKernelGGL(k_solve_many_bwd<true>, dim3(nt), dim3(256), 0, st, t, Lsx, Lsi, x, sync, ticket, info, Tbase);
-    else hipLaunchKernelGGL(k_solve_many_bwd<false>, dim3(nt), dim3(256), 0, st, t, Lsx, Lsi, x, sync, ticket, info, Tbase);
-}
-void launch_solve_many_pack(const double* Bc, int64_t n, int cw, double* X, hipStream_t st) {
-    const int64_t m = n * SVM_W;
-    if (m > 0) hipLaunchKernelGGL(k_solve_many_pack, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, Bc, n, cw, X);
-}
-void launch_solve_many_unpack(const double* X, int64_t n, int cw, double* Bc, hipStream_t st) {
-    const int64_t m = n * cw;
-    if (m > 0) hipLaunchKernelGGL(k_solve_many_unpack, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, X, n, cw, Bc);
 }
 
 // ---------------------------------------------------------------------------------------------------

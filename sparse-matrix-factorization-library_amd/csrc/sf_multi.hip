@@ -440,7 +440,7 @@ int sf_comm_allreduce_sum(sf_comm* c, void* device_buf, sf_long count, void* str
 // parent-front merge (one all-reduce of the packed block columns) and the segment's launches.  host_out != NULL: the
 // pieces of the factor this rank is responsible for are copied into it while the factorization runs.
 // The solve with a factor that stays distributed over the ranks' mapped plans (create_mapped), after
-// sf_chol_plan_factorize_distributed: see the schedule in sf_chol_plan.hip ("distributed solve").  b_host: the whole right-hand
+// sf_chol_plan_factorize_distributed: see the schedule in sf_plan_build.hip and the drivers in sf_solve.hip.  b_host: the whole right-hand
 // side (permuted numbering) on every rank; x_host: every rank writes the entries it is responsible for (its subtrees' columns, and
 // the columns of the shared supernodes whose group it leads) and leaves the others alone -- ranks that are threads of one process
 // may share one x_host, separate processes merge theirs (the entries of a column range come from exactly one rank).
@@ -464,17 +464,12 @@ int sf_chol_plan_solve_distributed(sf_chol_plan* p, sf_comm* comm, const sf_floa
         for (const auto& r : p->solve_load)
             memcpy(xb.data() + r.first, b_host + r.first, (size_t)(r.second - r.first) * sizeof(double));
         if (hipMemcpyAsync(p->d_x, xb.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) rc = SF_ERR_HIP;
-        if (!rc && p->d_solve_sync &&
-            hipMemsetAsync(p->d_solve_sync, 0, (size_t)(1 + p->n_solve_sync + sf_chol_plan::SOLVE_TICKETS * nst) * sizeof(int), st) != hipSuccess)
-            rc = SF_ERR_HIP;
+        if (!rc && p->d_solve_sync && hipMemsetAsync(p->d_solve_sync, 0, sf_solve_sync(p).bytes, st) != hipSuccess) rc = SF_ERR_HIP;
     }
     if (!rc && injected(p->rank, 3)) rc = SF_ERR_HIP;
     if ((rc = agree_status(p, comm, rc, st))) return rc;
     if (idle) return SF_OK;               // a rank that stores nothing (more ranks than subtrees) reports nothing
-    const double* fwd_base = p->d_Lsx;
-    const double* bwd_base = p->lu ? p->d_Lsx + p->xC : p->d_Lsx;
-    int* sync = p->d_solve_sync + 1;
-    int* tickets = sync + p->n_solve_sync;
+    const SolveSync y = sf_solve_sync(p);
     for (size_t k = 0; k < nst; ++k) {
         const auto& s = p->solve_steps[k];
         if (!rc && k > 0 && injected(p->rank, 4)) rc = SF_ERR_HIP;
@@ -487,18 +482,14 @@ int sf_chol_plan_solve_distributed(sf_chol_plan* p, sf_comm* comm, const sf_floa
             if (rc) { if (gc->kind == 1) (void)sf_comm_allreduce_sum(gc, nullptr, -1, (void*)st); continue; }
             rc = sf_comm_allreduce_sum(gc, (void*)(p->d_x + R.off), R.cnt, (void*)st);
         }
-        if (!rc) sf_solve_step_fwd(p, k, fwd_base, sync, tickets, st);
+        if (!rc) sf_solve_step_fwd(p, k, p->d_Lsx, p->d_x, 1, y, st);
     }
     if (rc) abort_comm(comm);
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    sf::launch_solve_transpose_diag(p->d_solve, p->d_solveT_list, p->n_solveT, bwd_base, p->d_solveT, st);      // see sf_chol_plan_solve
-    for (size_t k = nst; k-- > 0;) sf_solve_step_bwd(p, k, bwd_base, sync, tickets, st);
+    sf_solve_sweep_bwd(p, p->d_x, 1, true, y, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(xb.data(), p->d_x, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    int sinfo = 0;
-    if (p->d_solve_sync) HIP_TRY(hipMemcpyAsync(&sinfo, p->d_solve_sync, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (sinfo) return SF_ERR_HIP;
+    if ((rc = sf_solve_finish(p, st))) return rc;
     for (const auto& r : p->solve_own)
         memcpy(x_host + r.first, xb.data() + r.first, (size_t)(r.second - r.first) * sizeof(double));
     return SF_OK;

@@ -1399,8 +1399,7 @@ static int create_device_resources(const PlanInput& in, const PlanKnobs& kn, con
             p.bytes_device += (size_t)T.solveT_size * sizeof(double);
             p.n_solveT = (int64_t)T.solveT_list.size();
         }
-        // sync words of the solve: [0] status, then the flags / counters, then two launch tickets per step
-        const size_t sb = (size_t)(1 + p.n_solve_sync + sf_chol_plan::SOLVE_TICKETS * p.solve_steps.size()) * sizeof(int);
+        const size_t sb = sf_solve_sync(&p).bytes;      // (the block's layout: sf_solve.hip)
         if (!dalloc((void**)&p.d_solve_sync, sb)) return SF_ERR_ALLOC;
         p.bytes_device += sb;
         if (!dalloc((void**)&p.d_x, std::max<int64_t>(in.n, 1) * sizeof(double))) return SF_ERR_ALLOC;

@@ -112,11 +112,27 @@ struct DlPiece {
 extern "C" void sf_plan_offer_factor_buffer(double* ptr, size_t bytes);
 extern "C" int sf_plan_factor_borrowed(const sf_chol_plan* p);
 
+// hipEventElapsedTime whose failure (an event that was never recorded) is expected and must not stay behind as the thread's
+// "last error": callers that poll hipGetLastError after their own launches (PyTorch does) would report it as theirs
+static inline bool elapsed_ms(float* ms, hipEvent_t a, hipEvent_t b) {
+    if (hipEventElapsedTime(ms, a, b) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
 struct sf_comm;      // one rank's end of a multi-GPU group (sf_multi.hip)
 struct sf_chol_plan;
-// one step of the solve sweeps (sf_chol_plan.hip; shared by sf_chol_plan_solve and sf_chol_plan_solve_distributed)
-void sf_solve_step_fwd(sf_chol_plan* p, size_t k, const double* base, int* sync, int* tickets, hipStream_t st);
-void sf_solve_step_bwd(sf_chol_plan* p, size_t k, const double* base, int* sync, int* tickets, hipStream_t st);
+// ---- the device solve's host side (sf_solve.hip; shared by sf_chol_plan_solve[_many] and sf_chol_plan_solve_distributed) ----
+// the plan's sync block d_solve_sync: the info word, n_solve_sync sync words, SOLVE_TICKETS ticket words per step; bytes: all of it
+struct SolveSync { int *info, *sync, *tickets; size_t bytes; };
+SolveSync sf_solve_sync(const sf_chol_plan* p);
+// one step of a sweep on x (width 1: x[n]; sf::SVM_W: the row-major block), base = the panels the sweep reads
+void sf_solve_step_fwd(sf_chol_plan* p, size_t k, const double* base, double* x, int width, const SolveSync& y, hipStream_t st);
+void sf_solve_step_bwd(sf_chol_plan* p, size_t k, const double* base, double* x, int width, const SolveSync& y, hipStream_t st);
+// the backward half: the row-major copies of the top steps' diagonal blocks (transpose_diag), then every step from the last
+void sf_solve_sweep_bwd(sf_chol_plan* p, double* x, int width, bool transpose_diag, const SolveSync& y, hipStream_t st);
+// the end of a solve: read the info word, synchronize; SF_ERR_HIP if a bounded in-launch wait ran out
+int sf_solve_finish(sf_chol_plan* p, hipStream_t st);
 
 struct sf_chol_plan {
     // ---- overlapped download schedule (built once) and the state of a running download ----

@@ -5,6 +5,13 @@
 
 namespace sf {
 
+// v of lane l (uniform)
+__device__ __forceinline__ double readlane_f64(double v, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+}
+
 // max over the 64 lanes of a wave, result uniform.  DPP reduction: row_shr 1/2/4/8 inside the four rows of 16 lanes, then
 // row_bcast:15 and row_bcast:31 carry the row maxima up to lane 63 (gfx9 DPP controls 0x111.., 0x142, 0x143).  Lanes with no
 // source keep `old` = 0, the identity of an unsigned max.

@@ -7,6 +7,7 @@ rounding is far below the bounds.  Every bound is per ELEMENT, of the form the a
     POTRF          |A - L^ L^T|   <= SAFETY (b + 2) u |L^| |L^T|
     GETRF          |PA - L^ U^|   <= SAFETY (b + 2) u |L^| |U^|
     TRSM           |X^ D^T - B|   <= SAFETY (b + 2) u |X^| |D^T|
+    solve sweeps   |sum of an equation's terms - its right-hand side| <= SAFETY (terms) u (sum of the terms' magnitudes)
 A max-normalised metric (max error / max |ref|) would hide an error in a row scaled by 1e-6; these do not.
 
 Arena: the tests place every operand in one fp64 host image (the probe copies it to the device, launches once and copies
@@ -165,3 +166,20 @@ def getrf_rule(A, tol, eps):
     L = np.tril(F, -1) + np.eye(b, dtype=LD)
     Uu = np.triu(F)
     return pos, L, Uu, perturbed, margin
+
+
+def assert_equations(total, rhs, nterms, mag, cols, what):
+    """one equation per element: `total` (longdouble: the sum of the equation's products, formed from the stored results)
+    against its right-hand side, |total - rhs| <= SAFETY nterms u mag with nterms = the number of terms of the sum and mag = the
+    sum of their magnitudes (|rhs| among them where rhs is itself a summand).  Only the columns `cols` are checked (the others may hold a planted NaN)."""
+    total, mag = np.asarray(total, dtype=LD)[:, cols], np.asarray(mag, dtype=LD)[:, cols]
+    rhs = np.asarray(rhs, dtype=LD)[:, cols]
+    if not np.all(np.isfinite(total)):
+        raise AssertionError(f"{what}: non-finite stored results at {np.argwhere(~np.isfinite(total))[:8].tolist()}")
+    err = np.abs(total - rhs)
+    bound = SAFETY * np.asarray(nterms, dtype=LD).reshape(-1, 1) * U * mag
+    viol = err > bound
+    if viol.any():
+        k = tuple(np.argwhere(viol)[0])
+        raise AssertionError(f"{what}: {int(viol.sum())} of {viol.size} equations beyond the bound, first at {list(k)} "
+                             f"(err {float(err[k]):.3e}, bound {float(bound[k]):.3e})")

@@ -9,6 +9,32 @@
 
 #include "sf_kernels.h"
 
+#ifdef KP_EIGHT_SOLVE_LAUNCHERS
+// The solve launchers as they were before they took the block width (one set per kernel family): with this defined the probe
+// builds against that sf_kernels.h, so the one-launch solve tests can be run on the kernels as they were before csrc/sf_solve.hip.
+namespace sf {
+inline void launch_solve_small_fwd(const SolveTask* t, int nt, int width, const double* Lsx, const int32_t* Lsi, double* x, int unit,
+                                   const int32_t* pivpos, hipStream_t st) {
+    if (width == 1) launch_solve_small_fwd(t, nt, Lsx, Lsi, x, unit, pivpos, st);
+    else launch_solve_many_small_fwd(t, nt, Lsx, Lsi, x, unit, pivpos, st);
+}
+inline void launch_solve_small_bwd(const SolveTask* t, int nt, int width, const double* Lsx, const int32_t* Lsi, double* x, hipStream_t st) {
+    if (width == 1) launch_solve_small_bwd(t, nt, Lsx, Lsi, x, st);
+    else launch_solve_many_small_bwd(t, nt, Lsx, Lsi, x, st);
+}
+inline void launch_solve_fwd(const SolveTask* t, int nt, int width, int big, const double* Lsx, const int32_t* Lsi, double* x, int unit,
+                             const int32_t* pivpos, int* sync, int* ticket, int* info, hipStream_t st) {
+    if (width == 1) launch_solve_fwd(t, nt, big, Lsx, Lsi, x, unit, pivpos, sync, ticket, info, st);
+    else launch_solve_many_fwd(t, nt, big, Lsx, Lsi, x, unit, pivpos, sync, ticket, info, st);
+}
+inline void launch_solve_bwd(const SolveTask* t, int nt, int width, int big, const double* Lsx, const int32_t* Lsi, double* x, int* sync,
+                             int* ticket, int* info, hipStream_t st, const double* Tbase) {
+    if (width == 1) launch_solve_bwd(t, nt, big, Lsx, Lsi, x, sync, ticket, info, st, Tbase);
+    else launch_solve_many_bwd(t, nt, big, Lsx, Lsi, x, sync, ticket, info, st, Tbase);
+}
+}  // namespace sf
+#endif
+
 namespace {
 
 // device copies of host arrays, freed on scope exit; the first failing HIP call is kept in `rc`
@@ -45,6 +71,7 @@ int kp_sizeof(const char* name) {
     if (!strcmp(name, "PotrfTask")) return (int)sizeof(sf::PotrfTask);
     if (!strcmp(name, "TrsmTask")) return (int)sizeof(sf::TrsmTask);
     if (!strcmp(name, "StepTask")) return (int)sizeof(sf::StepTask);
+    if (!strcmp(name, "SolveTask")) return (int)sizeof(sf::SolveTask);
     return -1;
 }
 
@@ -159,6 +186,58 @@ int kp_step(double* arena, int64_t narena, const sf::StepTask* tasks, int ntasks
     d.out(pivpos, pp, npiv);
     d.out(pivinv, pi, npiv);
     d.out(nperturb, np, 1);
+    return (int)d.rc;
+}
+
+// One step of the device solve: the forward launch on `tasks` (diagonal tasks first, then their row tiles; small != 0: the
+// narrow kernel, diagonal tasks only).  x: nx entries (width 1) or the row-major nx x SVM_W block (width SVM_W), in and out.
+// The probe owns the solve's words -- info, nsync sync words, one ticket -- zeroed before the launch; *info comes back.
+int kp_solve_fwd(double* arena, int64_t narena, const int32_t* Lsi, int64_t nLsi, double* x, int64_t nx, const sf::SolveTask* tasks,
+                 int ntasks, int width, int big, int small, int unit, const int32_t* pivpos, int64_t npiv, int nsync, int* info) {
+    Dev d;
+    double* A = d.in(arena, narena);
+    const int32_t* L = d.in(Lsi, nLsi);
+    double* X = d.in(x, nx * width);
+    const sf::SolveTask* T = d.in(tasks, ntasks);
+    const int32_t* pp = pivpos ? d.in(pivpos, npiv) : nullptr;
+    int* W = d.in<int>(nullptr, 2 + (int64_t)nsync);
+    if (d.rc == hipSuccess) {
+        int *sync = W + 1, *ticket = W + 1 + nsync;
+        if (small) sf::launch_solve_small_fwd(T, ntasks, width, A, L, X, unit, pp, 0);
+        else sf::launch_solve_fwd(T, ntasks, width, big, A, L, X, unit, pp, sync, ticket, W, 0);
+    }
+    d.finish();
+    d.out(arena, A, narena);
+    d.out(x, X, nx * width);
+    d.out(info, W, 1);
+    return (int)d.rc;
+}
+
+// The backward launch (row tiles first, then the diagonal tasks).  nT > 0: a scratch of nT doubles for the row-major copies of
+// the diagonal blocks of the tasks that carry a tdiag, made by launch_solve_transpose_diag in front of the launch.
+int kp_solve_bwd(double* arena, int64_t narena, const int32_t* Lsi, int64_t nLsi, double* x, int64_t nx, const sf::SolveTask* tasks,
+                 int ntasks, int width, int big, int small, int64_t nT, int nsync, int* info) {
+    Dev d;
+    double* A = d.in(arena, narena);
+    const int32_t* L = d.in(Lsi, nLsi);
+    double* X = d.in(x, nx * width);
+    const sf::SolveTask* T = d.in(tasks, ntasks);
+    int* W = d.in<int>(nullptr, 2 + (int64_t)nsync);
+    double* Tb = nT > 0 ? d.in<double>(nullptr, nT) : nullptr;
+    std::vector<int64_t> list;
+    for (int i = 0; Tb && i < ntasks; ++i)
+        if (tasks[i].nrows == 0 && tasks[i].tdiag) list.push_back(i);
+    const int64_t* dl = d.in(list.data(), (int64_t)list.size());
+    if (d.rc == hipSuccess) {
+        int *sync = W + 1, *ticket = W + 1 + nsync;
+        sf::launch_solve_transpose_diag(T, dl, (int64_t)list.size(), A, Tb, 0);
+        if (small) sf::launch_solve_small_bwd(T, ntasks, width, A, L, X, 0);
+        else sf::launch_solve_bwd(T, ntasks, width, big, A, L, X, sync, ticket, W, 0, Tb);
+    }
+    d.finish();
+    d.out(arena, A, narena);
+    d.out(x, X, nx * width);
+    d.out(info, W, 1);
     return (int)d.rc;
 }
 

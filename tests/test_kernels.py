@@ -1,11 +1,13 @@
-"""Single-launch tests of the numeric kernels of csrc/sf_kernels.hip against extended-precision references.
+"""Single-launch tests of the numeric kernels of csrc/sf_kernels.hip and of the device solve's kernels (csrc/sf_solve.hip)
+against extended-precision references.
 
 Every other GPU test reaches the kernels through a whole plan, i.e. only at the shapes the symbolic analysis of a few
 matrix families produces.  Here a test-only probe (tests/kernels/sf_kprobe.hip, built by the fixture below) runs ONE
 launch of a release launcher on task lists the test builds itself, in a host image of the factor arena whose guards and
 unread elements hold NaN (tests/kernel_ref.py).  Checked: per-element error bounds (operands scaled over 1e-6 .. 1e6),
 the read footprint (no NaN reaches a stored result), the write footprint (everything else bit-identical), the stream-K
-partition of k_gemm, pivot records, the load kernels, and the plan's validation of the matrix row indices.
+partition of k_gemm, pivot records, the load kernels, one step of the solve sweeps (diagonal tasks and row tiles in one
+launch), and the plan's validation of the matrix row indices.
 """
 import ctypes as C
 import os
@@ -34,6 +36,8 @@ STEP_TASK = np.dtype([("panel", "<i8"), ("xpanel", "<i8"), ("ld", "<i4"), ("J", 
                       ("pad", "<i4")])
 TRSM_TASK = np.dtype([("panel", "<i8"), ("dpanel", "<i8"), ("ld", "<i4"), ("diag", "<i4"), ("b", "<i4"), ("row0", "<i4"),
                       ("nrows", "<i4"), ("unit", "<i4"), ("first_col", "<i4"), ("pad", "<i4")])
+SOLVE_TASK = np.dtype([("panel", "<i8"), ("rows", "<i8"), ("ld", "<i4"), ("diag", "<i4"), ("b", "<i4"), ("row0", "<i4"), ("nrows", "<i4"),
+                       ("first_col", "<i4"), ("flag", "<i4"), ("expect", "<i4"), ("tdiag", "<i8")])
 
 
 def _make(args, timeout):
@@ -46,7 +50,8 @@ def test_probe_compiles(tmp_path):
     r = _make([f"OUT={tmp_path / 'libsf_kprobe.so'}"], 300)
     assert r.returncode == 0, r.stdout
     nm = subprocess.run(["nm", "-D", str(tmp_path / "libsf_kprobe.so")], stdout=subprocess.PIPE, text=True).stdout
-    for name in ("kp_gemm", "kp_update_small", "kp_potrf", "kp_getrf", "kp_trsm", "kp_step", "kp_build_loadmap"):
+    for name in ("kp_gemm", "kp_update_small", "kp_potrf", "kp_getrf", "kp_trsm", "kp_step", "kp_build_loadmap", "kp_solve_fwd",
+                 "kp_solve_bwd"):
         assert f" T {name}" in nm
 
 
@@ -196,7 +201,8 @@ def kp():
     r = _make([], 600)
     assert r.returncode == 0, r.stdout
     L = C.CDLL(os.path.join(KDIR, "libsf_kprobe.so"))
-    for name, dt in (("GemmProb", GEMM_PROB), ("GemmTask", GEMM_TASK), ("PotrfTask", POTRF_TASK), ("TrsmTask", TRSM_TASK), ("StepTask", STEP_TASK)):
+    for name, dt in (("GemmProb", GEMM_PROB), ("GemmTask", GEMM_TASK), ("PotrfTask", POTRF_TASK), ("TrsmTask", TRSM_TASK), ("StepTask", STEP_TASK),
+                     ("SolveTask", SOLVE_TASK)):
         assert L.kp_sizeof(name.encode()) == dt.itemsize, name
     vp, i64, i32, f64 = C.c_void_p, C.c_int64, C.c_int, C.c_double
     L.kp_gemm.argtypes = [vp, i64, vp, i32, vp, i32, vp, C.c_uint32, C.c_uint32, i32, vp, i64, i32, i32, i32]
@@ -206,6 +212,8 @@ def kp():
     L.kp_getrf.argtypes = [vp, i64, vp, i32, i64, vp, f64, f64, vp, vp, i64, vp]
     L.kp_trsm.argtypes = [vp, i64, vp, i32, vp, i64]
     L.kp_step.argtypes = [vp, i64, vp, i32, i32, vp, i32, i32, vp, i64, f64, f64, vp, vp, i64, vp]
+    L.kp_solve_fwd.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, vp, i64, i32, vp]
+    L.kp_solve_bwd.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, i64, i32, vp]
     L.kp_build_loadmap.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, i64, i32, vp]
     L.kp_load_mapped.argtypes = [vp, i64, vp, vp, i64]
     L.kp_load_panels.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp]
@@ -897,3 +905,244 @@ def test_load_kernels(kp, skip_diag):
     _ok(kp.kp_load_panels(P(a), len(a), P(Lp), P(Li), P(Lx), n, P(Super), P(SuperMap), ns, P(Lsip), P(Lsi), P(Lsxp + base),
                           skip_diag, P(mask)))
     assert np.array_equal(kr.bits(a), kr.bits(exp)), "k_load_panels"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the device solve (csrc/sf_solve.hip): one launch = one step of a sweep, the diagonal tasks and their row tiles together,
+# so the hand-off inside the launch is part of what is checked.  Every supernode of a case is one panel whose step is its
+# last column block (columns [diag, diag + b) of diag + b); the rows below it gather / scatter through Lsi into a tail of x
+# that the panels share (their atomics meet there).  What the launch may not read holds NaN: the arena outside the
+# triangle and the rows below, x outside the blocks and the gathered rows.
+# Checked as equations on the stored results, every sum formed in longdouble from the operands the kernel had
+# (kernel_ref.assert_equations: SAFETY u (number of terms) (sum of |terms|) per element; the tiles add with fp64 atomics in no
+# fixed order, so nothing is compared bit for bit).  The diagonal solves are checked by their residual, as test_trsm_blocks
+# checks X D^T = B, not by the distance to a longdouble solution: a bound of that form holds for the residual of a substitution
+# whatever the triangle's condition, and for the solution itself only with the condition number as a factor.
+#   forward  diagonal: sum_k M(i, k) y_k = x_i           M = the block as the sweep sees it (unit diagonal, pivot order)
+#            rows    : x'_g = x_g - sum over the panels and k of L(r, k) y_k
+#   backward         : sum_{c >= k} D(c, k) y_c + sum_r L(r, k) x_g(r) = x_k
+# ---------------------------------------------------------------------------------------------------------------------
+SV_ROWS, SVM_W = 64, 16
+SOLVE_B = [1, 63, 64, 65, 200, 256]
+SOLVE_BELOW = [0, 1, 64, 65]
+SOLVE_FAR = 130                 # rows of a far tile: ONE task of three row groups (64, 64, 2)
+SOLVE_TAIL = 200
+SOLVE_NARROW = [(1, 100, False), (37, 0, False), (64, 1, False), (37, 64, False), (64, 100, False)]      # five tasks: two workgroups
+SOLVE_NAN_COL = 5
+
+
+def _solve_shapes(big):
+    """(b, rows below, far) of a general launch.  The <false> instantiations have no barrier between the 64-column sub-blocks, so
+    a DIAGONAL task of b > 64 is outside their contract: a step with such a panel is launched with big = 1 (sf_plan_build.hip:
+    big |= b > NB; the forward launch and the fused backward launch hold the step's diagonal tasks and tiles together), and only
+    big steps carry far tiles.  The one way <false> meets b > 64 is the two-launch backward form, whose first launch holds the row
+    tiles alone: test_solve_bwd_tiles_alone."""
+    shapes = [(b, below, False) for b in SOLVE_B if big or b <= NB for below in SOLVE_BELOW]
+    if big:
+        shapes += [(65, SOLVE_FAR, True), (256, SOLVE_FAR, True)]
+    return shapes
+
+
+def _solve_case(rng, shapes, width, narrow=False, pivot=False, nan_col=None):
+    ar = kr.Arena()
+    panels, lsi, col = [], [], 0
+    for i, (b, below, far) in enumerate(shapes):
+        diag = 0 if narrow else 1 + i % 3
+        nscol, nsrow = diag + b, diag + b + below
+        ld = nsrow if narrow else nsrow + 5             # the narrow kernels take ld = nsrow as the row count
+        # (off-diagonal entries ~ 1 / sqrt(b): a random triangle's substitution otherwise grows exponentially with b)
+        D = np.tril(rng.uniform(-1, 1, (b, b)), -1) * (2 / np.sqrt(b)) + np.diag(rng.uniform(1, 2, b) * rng.choice([-1, 1], b))
+        Lb = kr.scalings(rng, below)[:, None] * rng.uniform(-1, 1, (below, b))
+        pos = np.arange(b)
+        if pivot:
+            for s in range(0, b, NB):
+                pos[s:s + NB] = s + rng.permutation(min(NB, b - s))
+        panels.append(dict(b=b, below=below, far=far, diag=diag, nscol=nscol, nsrow=nsrow, ld=ld, off=ar.alloc(ld * nscol, skew=i % 2),
+                           first_col=col, blk=slice(col + diag, col + nscol), D=D, Lb=Lb, pos=pos))
+        col += nscol
+    nx = col + SOLVE_TAIL
+    x = np.full((nx, width), np.nan)
+    pivpos = np.arange(nx, dtype=np.int32)
+    for p in panels:
+        p["gi"] = col + np.sort(rng.choice(SOLVE_TAIL, p["below"], replace=False))
+        p["rows"] = len(lsi)
+        lsi += list(range(p["first_col"], p["first_col"] + p["nscol"])) + p["gi"].tolist()
+        x[p["blk"]] = kr.scalings(rng, p["b"])[:, None] * rng.uniform(-1, 1, (p["b"], width))
+        pivpos[p["blk"]] = p["blk"].start + p["pos"]
+    used = np.unique(np.concatenate([p["gi"] for p in panels]))
+    x[used] = kr.scalings(rng, len(used))[:, None] * rng.uniform(-1, 1, (len(used), width))
+    cols = np.arange(width)
+    if nan_col is not None:
+        x[:, nan_col] = np.nan
+        cols = cols[cols != nan_col]
+    return types.SimpleNamespace(ar=ar, panels=panels, lsi=np.array(lsi, dtype=np.int32), x=x, nx=nx, pivpos=pivpos, cols=cols)
+
+
+def _solve_arena(case, unit):
+    a = case.ar.image()
+    for p in case.panels:
+        b, ld, diag, off = p["b"], p["ld"], p["diag"], p["off"]
+        r, c = np.tril_indices(b, -1 if unit else 0)            # the upper triangle (and a unit diagonal) stay NaN
+        a[off + diag + r + (diag + c) * ld] = p["D"][r, c]
+        rr, cc = np.indices((p["below"], b))
+        a[off + p["nscol"] + rr + (diag + cc) * ld] = p["Lb"]
+    return a
+
+
+def _solve_tasks(case, backward, narrow=False, tdiag=False, tiles_only=False):
+    """the launch's task list as the plan orders it (producers first) and the size of the row-major copies' scratch"""
+    dg, tiles, nT = [], [], 0
+    for i, p in enumerate(case.panels):
+        if narrow:
+            dg.append((p["off"], p["rows"], p["nsrow"], 0, p["b"], 0, 0, p["first_col"], 0, 0, 0))
+            continue
+        head = (p["off"], p["rows"], p["ld"], p["diag"], p["b"])
+        flag = 2 * i + backward         # sync words of a (panel, step): [flag] forward "solved", [flag + 1] backward tile counter
+        rows = p["below"] if p["far"] else SV_ROWS
+        mine = [head + (p["nscol"] + r, min(rows, p["below"] - r), p["first_col"], flag, 0, 0) for r in range(0, p["below"], rows)]
+        td = 0
+        if tdiag and i % 2 == 0:        # every other panel: both address forms in one launch
+            td, nT = 1 + nT, nT + p["b"] * p["b"]
+        dg.append(head + (0, 0, p["first_col"], flag, len(mine), td))
+        tiles += mine
+    if tiles_only:
+        dg = []
+    return np.array(tiles + dg if backward else dg + tiles, dtype=SOLVE_TASK), nT
+
+
+def _solve_run(kp, case, a, tasks, backward, width, big, small, unit=0, pivot=False, nT=0):
+    x, before, info = case.x.copy(), a.copy(), np.full(1, -1, dtype=np.int32)
+    nsync = 2 * len(case.panels) + 1
+    if backward:
+        _ok(kp.kp_solve_bwd(P(a), len(a), P(case.lsi), len(case.lsi), P(x), case.nx, P(tasks), len(tasks), width, big, small, nT, nsync,
+                            P(info)))
+    else:
+        _ok(kp.kp_solve_fwd(P(a), len(a), P(case.lsi), len(case.lsi), P(x), case.nx, P(tasks), len(tasks), width, big, small, unit,
+                            P(case.pivpos) if pivot else None, case.nx, nsync, P(info)))
+    assert info[0] == 0, info
+    assert np.array_equal(kr.bits(before), kr.bits(a)), "the factor arena changed"
+    return x
+
+
+def _solve_check_fwd(case, x1, unit, what):
+    x0 = case.x
+    written = np.zeros(x0.shape, dtype=bool)
+    tail, mag, cnt = x0.astype(kr.LD), np.abs(x0).astype(kr.LD), np.zeros(case.nx, dtype=np.int64)
+    for p in case.panels:
+        b, yh = p["b"], x1[p["blk"]]
+        S = np.tril(p["D"], -1) + np.eye(b) if unit else p["D"]
+        M = S.copy()
+        for s in range(0, b, NB):       # row l of a sub-block meets the diagonal block's row pos[l]; left of it, its own
+            M[s:s + NB, s:s + NB] = S[p["pos"][s:s + NB], s:s + NB]
+        kr.assert_equations(kr.matmul_ld(M, yh), x0[p["blk"]], (M != 0).sum(1), kr.matmul_ld(np.abs(M), np.abs(yh)), case.cols,
+                            f"{what} diagonal b={b}")
+        written[p["blk"]] = True
+        written[p["gi"]] = True
+        tail[p["gi"]] -= kr.matmul_ld(p["Lb"], yh)
+        mag[p["gi"]] += kr.matmul_ld(np.abs(p["Lb"]), np.abs(yh))
+        cnt[p["gi"]] += b
+    g = np.flatnonzero(cnt)
+    kr.assert_equations(x1[g], tail[g], cnt[g] + 1, mag[g], case.cols, f"{what} rows below")      # the products and x_g itself
+    kr.assert_unchanged(x0, x1, written, what)
+
+
+def _solve_check_bwd(case, x1, what):
+    x0 = case.x
+    written = np.zeros(x0.shape, dtype=bool)
+    for p in case.panels:
+        b, yh, xr, D, Lb = p["b"], x1[p["blk"]], x0[p["gi"]], p["D"], p["Lb"]
+        kr.assert_equations(kr.matmul_ld(D.T, yh) + kr.matmul_ld(Lb.T, xr), x0[p["blk"]], b - np.arange(b) + p["below"],
+                            kr.matmul_ld(np.abs(D.T), np.abs(yh)) + kr.matmul_ld(np.abs(Lb.T), np.abs(xr)), case.cols,
+                            f"{what} b={b} below={p['below']}")
+        written[p["blk"]] = True
+    kr.assert_unchanged(x0, x1, written, what)
+
+
+def _solve_name(width, direction, big=None):
+    return f"k_solve{'_many' if width > 1 else ''}" + (f"_small_{direction}" if big is None else f"_{direction}<{bool(big)}>")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("unit", [0, 1])
+@pytest.mark.parametrize("big", [0, 1])
+@pytest.mark.parametrize("width", [1, SVM_W])
+def test_solve_fwd_step(kp, width, big, unit):
+    case = _solve_case(np.random.default_rng(31 + 4 * big + unit), _solve_shapes(big), width)
+    tasks, _ = _solve_tasks(case, 0)
+    x1 = _solve_run(kp, case, _solve_arena(case, unit), tasks, 0, width, big, 0, unit=unit)
+    _solve_check_fwd(case, x1, unit, f"{_solve_name(width, 'fwd', big)} unit={unit}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width", [1, SVM_W])
+def test_solve_fwd_step_pivoting(kp, width):
+    """LU with pivoting: x_blk is brought into pivot order sub-block by sub-block as the sweep reaches it"""
+    case = _solve_case(np.random.default_rng(41), [(65, 65, False), (200, 64, False)], width, pivot=True)
+    tasks, _ = _solve_tasks(case, 0)
+    x1 = _solve_run(kp, case, _solve_arena(case, 1), tasks, 0, width, 1, 0, unit=1, pivot=True)
+    _solve_check_fwd(case, x1, 1, f"{_solve_name(width, 'fwd', 1)} pivoting")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tdiag", [False, True])
+@pytest.mark.parametrize("big", [0, 1])
+@pytest.mark.parametrize("width", [1, SVM_W])
+def test_solve_bwd_step(kp, width, big, tdiag):
+    case = _solve_case(np.random.default_rng(51 + 4 * big + tdiag), _solve_shapes(big), width)
+    tasks, nT = _solve_tasks(case, 1, tdiag=tdiag)
+    x1 = _solve_run(kp, case, _solve_arena(case, 0), tasks, 1, width, big, 0, nT=nT)
+    _solve_check_bwd(case, x1, f"{_solve_name(width, 'bwd', big)} tdiag={tdiag}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width", [1, SVM_W])
+def test_solve_bwd_tiles_alone(kp, width):
+    """the two-launch backward form (solve_bwd_fused off) launches a step's row tiles alone with big = 0, whatever the step's
+    width: <false> with b > 64, waves 1 - 3 at work.  x_blk' = x_blk - L^T x[rows]; nothing waits, the counters just count."""
+    shapes = [(b, below, False) for b in (65, 200, 256) for below in (1, 64, 65)]
+    case = _solve_case(np.random.default_rng(91), shapes, width)
+    tasks, _ = _solve_tasks(case, 1, tiles_only=True)
+    x1 = _solve_run(kp, case, _solve_arena(case, 0), tasks, 1, width, 0, 0)
+    x0, what = case.x, f"{_solve_name(width, 'bwd', 0)} tiles alone"
+    written = np.zeros(x0.shape, dtype=bool)
+    for p in case.panels:
+        xr, Lb = x0[p["gi"]], p["Lb"]
+        kr.assert_equations(x1[p["blk"]], x0[p["blk"]].astype(kr.LD) - kr.matmul_ld(Lb.T, xr), np.full(p["b"], p["below"] + 1),
+                            np.abs(x0[p["blk"]]) + kr.matmul_ld(np.abs(Lb.T), np.abs(xr)), case.cols, f"{what} b={p['b']} below={p['below']}")
+        written[p["blk"]] = True
+    kr.assert_unchanged(x0, x1, written, what)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["unit0", "unit1", "pivoting"])
+@pytest.mark.parametrize("width", [1, SVM_W])
+def test_solve_small_fwd(kp, width, mode):
+    unit, pivot = int(mode != "unit0"), mode == "pivoting"
+    case = _solve_case(np.random.default_rng(61 + unit), SOLVE_NARROW, width, narrow=True, pivot=pivot)
+    tasks, _ = _solve_tasks(case, 0, narrow=True)
+    x1 = _solve_run(kp, case, _solve_arena(case, unit), tasks, 0, width, 0, 1, unit=unit, pivot=pivot)
+    _solve_check_fwd(case, x1, unit, f"{_solve_name(width, 'fwd')} {mode}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width", [1, SVM_W])
+def test_solve_small_bwd(kp, width):
+    case = _solve_case(np.random.default_rng(71), SOLVE_NARROW, width, narrow=True)
+    tasks, _ = _solve_tasks(case, 1, narrow=True)
+    x1 = _solve_run(kp, case, _solve_arena(case, 0), tasks, 1, width, 0, 1)
+    _solve_check_bwd(case, x1, _solve_name(width, "bwd"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kernel", ["fwd", "bwd", "small_fwd", "small_bwd"])
+def test_solve_many_columns_are_independent(kp, kernel):
+    """one of the SVM_W right-hand sides is NaN throughout: every other column still meets its bound"""
+    narrow, backward = kernel.startswith("small"), kernel.endswith("bwd")
+    shapes = SOLVE_NARROW if narrow else [(64, 1, False), (65, 65, False), (256, SOLVE_FAR, True)]
+    case = _solve_case(np.random.default_rng(81), shapes, SVM_W, narrow=narrow, nan_col=SOLVE_NAN_COL)
+    tasks, nT = _solve_tasks(case, int(backward), narrow=narrow, tdiag=True)
+    x1 = _solve_run(kp, case, _solve_arena(case, 0), tasks, int(backward), SVM_W, int(not narrow), int(narrow), nT=nT)
+    if backward:
+        _solve_check_bwd(case, x1, f"k_solve_many_{kernel} with a NaN column")
+    else:
+        _solve_check_fwd(case, x1, 0, f"k_solve_many_{kernel} with a NaN column")

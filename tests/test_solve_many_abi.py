@@ -1,5 +1,5 @@
 """The multi-right-hand-side solve's C ABI without a device: exported symbols, argument checks that run before anything
-touches a device, and zero scratch for the new solve kernels."""
+touches a device, and zero scratch for the device solve's kernels."""
 import ctypes as C
 import os
 import re
@@ -73,8 +73,8 @@ def test_out_of_core_schedule_refused():
 
 
 def test_solve_many_kernels_use_no_scratch(tmp_path):
-    """sf_kernels.hip compiled device-only for gfx950: every multi-right-hand-side solve kernel reports zero scratch"""
-    src = os.path.join(ROOT, "sparse-matrix-factorization-library_amd", "csrc", "sf_kernels.hip")
+    """sf_solve.hip compiled device-only for gfx950: every solve kernel, of both families, reports zero scratch"""
+    src = os.path.join(ROOT, "sparse-matrix-factorization-library_amd", "csrc", "sf_solve.hip")
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "--cuda-device-only", "-c", "-O3", "-std=c++17", "-munsafe-fp-atomics",
                         "-I" + os.path.join(ROOT, "include"), "-Rpass-analysis=kernel-resource-usage", src, "-o", str(tmp_path / "k.o")],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
@@ -91,4 +91,6 @@ def test_solve_many_kernels_use_no_scratch(tmp_path):
             scratch[name] = int(m.group(1))
     many = {k: v for k, v in scratch.items() if "k_solve_many" in k}
     assert len(many) == 8, sorted(many)         # fwd / bwd x (BIG, not BIG), small fwd / bwd, pack, unpack
-    assert all(v == 0 for v in many.values()), many
+    solve = {k: v for k, v in scratch.items() if "k_solve" in k}
+    assert len(solve) == 15, sorted(solve)      # + the single-vector six and the transpose of the diagonal blocks
+    assert all(v == 0 for v in solve.values()), solve
