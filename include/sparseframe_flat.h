@@ -150,6 +150,35 @@ int sf_chol_plan_logdet(sf_chol_plan *plan, sf_float *out);
 /* SparseFrame_validate on the device (C:3141-3266; LU plans: L:3702-3858): b_i = 1 + i/n, solve with the resident factor,
  * r = A x - b from the plan's copy of the matrix values, *residual = |r|_inf / (|A|_1 |x|_inf + |b|_inf).  x_host may be NULL. */
 int sf_chol_plan_validate(sf_chol_plan *plan, sf_float *residual, sf_float *x_host);
+/* r = b - A x on the device with the plan's CURRENT matrix values (the last set_values; permuted space), for the caller's own b
+ * and x.  With w = |A| |x| + |b|:
+ *     *berr = max_i |r_i| / w_i over the rows with w_i > 0     (componentwise backward error, as LAPACK xPORFS / xGERFS report it)
+ *     *nerr = |r|_inf / (|A|_1 |x|_inf + |b|_inf)              (the number sf_chol_plan_validate reports)
+ * If any r_i, x_i or b_i is not finite, both come back not finite (NaN), never a finite value that hides it.  r_host, berr, nerr
+ * may each be NULL.  Plain fp64 with FMA, one pass over the rows of A in a fixed summation order: the same b and x give the same
+ * bits on every call.  An entry given more than once in its column counts as the factorization counts it (the last one); an
+ * unsymmetric LU plan takes the diagonal from U, as its factorization does.  Needs set_values only, no factorization.
+ * Whole, resident plans (schedule-only, partial, sharded, mapped and out-of-core plans: SF_ERR_ARG).  The row form of A --
+ * positions into the plan's value arrays, so a later set_values needs no rebuild -- and the work vectors are allocated by the
+ * first residual / refine call and kept (stat "bytes_refine", not in "bytes_device"; SF_ERR_ALLOC leaves the plan usable). */
+int sf_chol_plan_residual(sf_chol_plan *plan, const sf_float *b_host, const sf_float *x_host,
+                          sf_float *r_host /* or NULL */, sf_float *berr /* or NULL */, sf_float *nerr /* or NULL */);
+/* Iterative refinement on the device: x0 = solve(b), then at most max_iter steps  r = b - A x;  d = solve(r);  x += d.
+ * Before step k (k = 0, 1, ...) the loop stops if berr_k <= tol (tol <= 0: 2^-52), if k == max_iter, if berr_k is not finite, or if
+ * k >= 1 and berr_k > berr_{k-1} / 2 (stagnation).  x_host receives the iterate with the SMALLEST finite berr seen (kept in a
+ * second device vector) and *berr that value; if berr_0 is not finite, x0 and that berr -- the return code stays SF_OK.
+ * max_iter == 0: the plain solve plus its berr.  max_iter < 0, NULL b or x: SF_ERR_ARG.  x_host may be b_host.
+ * The solves use the RESIDENT factor, the residual the CURRENT values: the last factorization that was started must have
+ * succeeded, but it need NOT be a factorization of the current values -- set_values after factorize is allowed and refines
+ * towards the new matrix with the old factor as preconditioner (values that drift over time steps, one factorization kept).
+ * Per step one 48-byte copy and one synchronisation; b, x, r, w and the best x stay on the device.  Same plans as residual.
+ * Stats: "last_refine_iters" (solves after the first), "last_refine_berr0", "last_refine_berr", "last_refine_ms" (device
+ * time from events, the copies of b and x excluded), "bytes_refine". */
+int sf_chol_plan_refine(sf_chol_plan *plan, const sf_float *b_host, sf_float *x_host,
+                        int max_iter, double tol, sf_float *berr /* or NULL */);
+/* w = |A| |x| + |b| (n doubles) of the last residual evaluation of this plan (a residual call, or the last step of a refine
+ * call); Cholesky and LU plans; SF_ERR_ARG before the first one */
+int sf_chol_plan_residual_weights(sf_chol_plan *plan, sf_float *w_host);
 /* statistics: "levels","launches","gemm_tasks","update_pairs","flops_exec","flops_update",
  * "scatter_elems","bytes_device","last_ms" (device time of the last factorize, HIP events),
  * "last_update_ms","last_panel_ms","last_load_ms" (only when profiling is on) */
@@ -349,7 +378,7 @@ int sf_lu_plan_set_values(sf_lu_plan *plan, const sf_float *Lx, const sf_float *
  * L:3344, static pre-pivot L:589-673 disabled).  The symbolic structure is static, so rows can only be exchanged where that
  * keeps the structure: INSIDE the 64 x 64 diagonal block of a 64-column step.  Threshold partial pivoting there -- the natural
  * row keeps the pivot while |a_jj| >= tol * max over the block's unused rows of |a_ij| -- and a pivot smaller than
- * perturb * max|a_ij| is replaced by +- that value ("perturbed_pivots" stat; refine the solution iteratively then).
+ * perturb * max|a_ij| is replaced by +- that value ("perturbed_pivots" stat; refine the solution then: sf_lu_plan_refine).
  * tol in [0, 1]: 0 = no pivoting (exactly the reference's behaviour; a zero pivot is SF_ERR_NOT_POSDEF when perturb is 0 too),
  * 1 = partial pivoting.  Defaults: tol 0, perturb 0 = the reference (env SF_LU_PIVOT_TOL at plan creation: that tol and perturb sqrt(eps); SF_LU_PERTURB).  On a
  * matrix whose natural pivots pass the threshold (e.g. diagonally dominant) the factor is bit-identical to the no-pivot one.
@@ -367,6 +396,12 @@ int sf_lu_plan_get_factor(sf_lu_plan *plan, sf_float *Lsx);
 int sf_lu_plan_solve(sf_lu_plan *plan, const sf_float *b_host, sf_float *x_host);
 /* sf_chol_plan_solve_many for an LU plan: X <- (L U)^{-1} B, the plan's pivots applied when pivoting is on */
 int sf_lu_plan_solve_many(sf_lu_plan *plan, sf_long nrhs, const sf_float *B, sf_long ldb, sf_float *X, sf_long ldx);
+/* sf_chol_plan_residual / sf_chol_plan_refine for an LU plan (the solves apply the plan's pivots when pivoting is on); a Cholesky
+ * plan is refused (SF_ERR_ARG) */
+int sf_lu_plan_residual(sf_lu_plan *plan, const sf_float *b_host, const sf_float *x_host,
+                        sf_float *r_host /* or NULL */, sf_float *berr /* or NULL */, sf_float *nerr /* or NULL */);
+int sf_lu_plan_refine(sf_lu_plan *plan, const sf_float *b_host, sf_float *x_host,
+                      int max_iter, double tol, sf_float *berr /* or NULL */);
 double sf_lu_plan_stat(const sf_lu_plan *plan, const char *name);
 int sf_lu_plan_set_profiling(sf_lu_plan *plan, int on);
 int sf_lu_plan_destroy(sf_lu_plan *plan);

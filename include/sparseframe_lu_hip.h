@@ -123,7 +123,7 @@ int SparseFrame_factorize_supernodal(struct common_info_struct *common_info, str
  * not -- a consumer of Lsx must apply the interchanges block by block in its forward sweep (LINPACK-style), as
  * SparseFrame_solve_supernodal here does; a consumer that ignores PivInv gets a wrong x whenever PivInv is not the identity.
  * SparseFrame_perturbed_pivots: how many pivots the last factorization into this matrix_info's Lsx replaced (0 = the factor is
- * exact; > 0: refine the solution iteratively; -1 unknown). */
+ * exact; > 0: refine the solution iteratively -- the plan ABI does it on the device, sf_lu_plan_refine in sparseframe_flat.h; -1 unknown). */
 int SparseFrame_set_pivoting(double tol, double perturb);
 /* the same for ONE matrix_info (overrides the process-wide setting for that matrix; dropped by SparseFrame_initialize_matrix /
  * _cleanup_matrix).  The reference's driver factorizes MATRIX_THREAD_NUM matrices at a time over one handler list (L:3375): each

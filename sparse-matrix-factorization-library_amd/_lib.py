@@ -126,6 +126,14 @@ lib.sf_handlers_plan_builds.argtypes = [C.c_void_p, C.c_int]
 lib.sf_handlers_plan_builds.restype = C.c_int64
 lib.sf_chol_plan_validate.argtypes = [C.c_void_p, c_double_p, c_double_p]
 lib.sf_chol_plan_validate.restype = C.c_int
+for _n in ("sf_chol_plan_residual", "sf_lu_plan_residual"):
+    getattr(lib, _n).argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
+    getattr(lib, _n).restype = C.c_int
+lib.sf_chol_plan_residual_weights.argtypes = [C.c_void_p, c_double_p]
+lib.sf_chol_plan_residual_weights.restype = C.c_int
+for _n in ("sf_chol_plan_refine", "sf_lu_plan_refine"):
+    getattr(lib, _n).argtypes = [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_double, c_double_p]
+    getattr(lib, _n).restype = C.c_int
 lib.sf_chol_plan_stat.argtypes = [C.c_void_p, C.c_char_p]
 lib.sf_chol_plan_stat.restype = C.c_double
 lib.sf_chol_plan_set_profiling.argtypes = [C.c_void_p, C.c_int]

@@ -401,7 +401,48 @@ class _ValidateMixin:
         return (res.value, x[:self.n]) if return_x else res.value
 
 
-class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin):
+class _RefineMixin:
+    """residual and iterative refinement on the device (sf_chol_plan_residual / _refine, sf_lu_plan_*)"""
+
+    def _refine_fn(self, what):
+        return getattr(lib, ("sf_lu_plan_" if isinstance(self, LUPlan) else "sf_chol_plan_") + what)
+
+    def residual(self, b, x):
+        """(r, berr, nerr) for the plan's current values, permuted space: r = b - A x, berr = max_i |r_i| / (|A| |x| + |b|)_i,
+        nerr = |r|_inf / (|A|_1 |x|_inf + |b|_inf); berr and nerr are NaN when r, x or b holds a non-finite entry"""
+        b, x = _f64(b), _f64(x)
+        if b.shape != (self.n,) or x.shape != (self.n,):
+            raise ValueError(f"residual: b and x must have shape ({self.n},)")
+        r = np.empty(max(self.n, 1), dtype=np.float64)
+        berr, nerr = C.c_double(), C.c_double()
+        fn = self._refine_fn("residual")
+        check(fn(self._h, _dp(b), _dp(x), _dp(r), C.byref(berr), C.byref(nerr)), fn.__name__)
+        return r[:self.n], berr.value, nerr.value
+
+    def residual_weights(self):
+        """w = |A| |x| + |b| of the plan's last residual evaluation"""
+        w = np.empty(max(self.n, 1), dtype=np.float64)
+        check(lib.sf_chol_plan_residual_weights(self._h, _dp(w)), "sf_chol_plan_residual_weights")
+        return w[:self.n]
+
+    def refine(self, b, max_iter=5, tol=0.0, return_info=False):
+        """x = solve(b) followed by at most max_iter refinement steps against the plan's current values (stops at berr <= tol,
+        tol <= 0: 2^-52, or on stagnation); the iterate with the smallest berr is returned.
+        return_info: (x, {"iters", "berr0", "berr"})"""
+        b = _f64(b)
+        if b.shape != (self.n,):
+            raise ValueError(f"refine: b must have shape ({self.n},)")
+        x = np.empty(max(self.n, 1), dtype=np.float64)
+        berr = C.c_double()
+        fn = self._refine_fn("refine")
+        check(fn(self._h, _dp(b), _dp(x), int(max_iter), float(tol), C.byref(berr)), fn.__name__)
+        x = x[:self.n]
+        if not return_info:
+            return x
+        return x, {"iters": int(self.stat("last_refine_iters")), "berr0": self.stat("last_refine_berr0"), "berr": berr.value}
+
+
+class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin):
     """Device-resident supernodal Cholesky (flat ABI).  Raises if no HIP device is present.
     phase/load_top: multi-GPU sharding (sf_chol_plan_create_sharded); default = the whole matrix on one device.
     rank/nranks (with phase): distributed top (sf_chol_plan_create_distributed), run with factorize_phase(0) and then
@@ -517,7 +558,7 @@ class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin):
         self.close()
 
 
-class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin):
+class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin):
     """Device-resident supernodal no-pivot LU (flat ABI, sf_lu_plan_*).  `sym` comes from analyze(..., method='lu').
     phase/load_top/rank/nranks: distributed multi-GPU plan (sf_lu_plan_create_distributed), as CholPlan."""
 

@@ -50,7 +50,8 @@ int sf_chol_plan_destroy(sf_chol_plan* p) {
     void* ptrs[] = {p->d_Lp, p->d_Li, p->d_Lx, p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, p->d_Lsxp,
                     p->d_Lsx, p->d_info, p->d_potrf, p->d_trsm, p->d_steps, p->d_flags, p->d_tinv, p->d_probs, p->d_gtasks, p->d_stasks, p->d_ktprefix,
                     p->d_Up, p->d_Ui, p->d_Ux, p->d_Xp, p->d_pack, p->d_piv, p->d_resid, p->d_loadmask, p->d_loadmapL, p->d_loadmapU, p->d_solve, p->d_solve_sync, p->d_x, p->d_relmap, p->d_scratch, p->d_status, p->d_fill, p->d_solveT, p->d_solveT_list, p->d_xm,
-                    p->d_sel, p->d_sel_diag, p->d_sel_units, p->d_sel_pairs, p->d_sel_scratch};
+                    p->d_sel, p->d_sel_diag, p->d_sel_units, p->d_sel_pairs, p->d_sel_scratch,
+                    p->d_rf_ptr, p->d_rf_col, p->d_rf_pos, p->d_rf_cptr, p->d_rf_ccol, p->d_rf_cpos, p->d_rf_vec};
     for (void* q : ptrs)
         if (q && !(q == (void*)p->d_Lsx && p->factor_borrowed)) (void)hipFree(q);      // (a borrowed factor buffer goes back to its lender)
     if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
@@ -1165,6 +1166,13 @@ double sf_chol_plan_stat(const sf_chol_plan* p, const char* name) {
     if (k == "last_selinv_ms") return p->last_selinv_ms;
     if (k == "flops_selinv") return p->flops_selinv;
     if (k == "selinv_valid") return (p->d_sel && p->sel_gen == p->factor_gen) ? 1.0 : 0.0;
+    if (k == "last_refine_iters") return (double)p->last_refine_iters;
+    if (k == "last_refine_berr0") return p->last_refine_berr0;
+    if (k == "last_refine_berr") return p->last_refine_berr;
+    if (k == "last_refine_ms") return p->last_refine_ms;
+    if (k == "last_residual_ms") return p->last_residual_ms;
+    if (k == "bytes_refine") return (double)p->bytes_refine;
+    if (k == "refine_row_entries") return (double)p->rf_entries;
     if (k == "perturbed_pivots") return (double)p->last_perturbed;
     if (k == "pivot_tol") return p->piv_tol;
     if (k == "last_to_host_ms") return p->last_to_host_ms;

@@ -217,6 +217,26 @@ constexpr int SEL_MAX_SLABS = 16;     // K slabs of the split products
 
 void launch_noop(hipStream_t st);
 
+// ---- residual and iterative refinement (sf_refine.hip, sf_chol_plan_residual / sf_chol_plan_refine) ----
+// A by rows (or by columns): run i = entries [ptr[i], ptr[i + 1]), entry e = (index col[e], value Vd[pos[e]] when pos[e] >= 0,
+// Vt[~pos[e]] otherwise) -- positions into the plan's value arrays, never copies of the values
+struct RefineForm {
+    const int64_t* ptr;
+    const int32_t* col;
+    const int64_t* pos;
+    const double *Vd, *Vt;
+};
+// r = b - A x and w = |A| |x| + |b|, one pass over the rows, a fixed summation order (no floating-point atomics)
+void launch_refine_resid(const RefineForm& rows, int64_t n, const double* x, const double* b, double* r, double* w, hipStream_t st);
+// *amax = max over the runs of the form of sum |value| (zero it first): |A|_1 from the column form
+void launch_refine_abs_sums(const RefineForm& f, int64_t n, double* amax, hipStream_t st);
+// s[0] = max_i |r_i| / w_i over w_i > 0, s[1] = |r|_inf, s[2] = |x|_inf, s[3] = |b|_inf, s[4] = flag word (bit 0: a non-finite r_i,
+// x_i or b_i; bit 1: *solve_info != 0); zero the five words first
+void launch_refine_norms(int64_t n, const double* r, const double* w, const double* x, const double* b, const int* solve_info, double* s,
+                         hipStream_t st);
+// save != 0: best <- x first; then x += d
+void launch_refine_update(int64_t n, double* x, const double* d, double* best, int save, hipStream_t st);
+
 // device twin of SparseFrame_validate's residual (C:3182-3263): b_i = 1 + i/n is written to b, r = A x - b, the four maxima
 // |r|_inf, |A|_1, |x|_inf, |b|_inf to norms[0..3] (zero them first).  Up == nullptr: (Lp, Li, Lx) is one triangle used symmetrically.
 void launch_residual(const int64_t* Lp, const int32_t* Li, const double* Lx, const int64_t* Up, const int32_t* Ui, const double* Ux,

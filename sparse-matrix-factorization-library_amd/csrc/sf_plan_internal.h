@@ -131,6 +131,8 @@ void sf_solve_step_fwd(sf_chol_plan* p, size_t k, const double* base, double* x,
 void sf_solve_step_bwd(sf_chol_plan* p, size_t k, const double* base, double* x, int width, const SolveSync& y, hipStream_t st);
 // the backward half: the row-major copies of the top steps' diagonal blocks (transpose_diag), then every step from the last
 void sf_solve_sweep_bwd(sf_chol_plan* p, double* x, int width, bool transpose_diag, const SolveSync& y, hipStream_t st);
+// both sweeps on x (the caller has zeroed the sync block on the stream)
+void sf_solve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, hipStream_t st);
 // the end of a solve: read the info word, synchronize; SF_ERR_HIP if a bounded in-launch wait ran out
 int sf_solve_finish(sf_chol_plan* p, hipStream_t st);
 
@@ -277,6 +279,16 @@ struct sf_chol_plan {
     double* d_sel_scratch = nullptr;
     size_t bytes_selinv = 0;
     double last_selinv_ms = 0, flops_selinv = 0;
+    // sf_chol_plan_residual / sf_chol_plan_refine (sf_refine.hip): A by rows as positions into d_Lx / d_Ux (unsymmetric LU: also by
+    // columns, for |A|_1), the vectors b | x | best x | r | w and the scalars; one set of allocations made by the first call
+    // (not in bytes_device).  rf_anorm_gen = factor_gen the stored |A|_1 belongs to.
+    int64_t *d_rf_ptr = nullptr, *d_rf_pos = nullptr, *d_rf_cptr = nullptr, *d_rf_cpos = nullptr;
+    int32_t *d_rf_col = nullptr, *d_rf_ccol = nullptr;
+    double* d_rf_vec = nullptr;
+    int64_t rf_entries = 0, rf_anorm_gen = -1;
+    size_t bytes_refine = 0;
+    int last_refine_iters = 0;
+    double last_refine_berr0 = 0, last_refine_berr = 0, last_refine_ms = 0, last_residual_ms = 0;
     int device = 0;
     int64_t n = 0, nsuper = 0, nnz = 0, isize = 0, xsize = 0;
     hipStream_t stream = nullptr;

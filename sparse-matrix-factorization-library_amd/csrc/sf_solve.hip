@@ -896,7 +896,7 @@ void sf_solve_sweep_bwd(sf_chol_plan* p, double* x, int width, bool transpose_di
     for (size_t k = p->solve_steps.size(); k-- > 0;) sf_solve_step_bwd(p, k, base, x, width, y, st);
 }
 
-static void solve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, hipStream_t st) {
+void sf_solve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, hipStream_t st) {
     const SolveSync y = sf_solve_sync(p);
     for (size_t k = 0; k < p->solve_steps.size(); ++k) sf_solve_step_fwd(p, k, p->d_Lsx, x, width, y, st);
     sf_solve_sweep_bwd(p, x, width, transpose_diag, y, st);
@@ -924,7 +924,7 @@ int sf_chol_plan_solve(sf_chol_plan* p, const sf_float* b_host, sf_float* x_host
     hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
     HIP_TRY(hipEventRecord(e0, st));
     HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, sf_solve_sync(p).bytes, st));
-    solve_sweeps(p, p->d_x, 1, true, st);
+    sf_solve_sweeps(p, p->d_x, 1, true, st);
     HIP_TRY(hipEventRecord(e1, st));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(x_host, p->d_x, p->n * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -970,7 +970,7 @@ int sf_chol_plan_solve_many(sf_chol_plan* p, sf_long nrhs, const sf_float* B, sf
         HIP_TRY(hipEventRecord(e0, st));
         sf::launch_solve_many_pack(stage, n, cw, p->d_xm, st);
         HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, sf_solve_sync(p).bytes, st));
-        solve_sweeps(p, p->d_xm, W, j0 == 0, st);       // (the row-major copies of the diagonal blocks: once per call)
+        sf_solve_sweeps(p, p->d_xm, W, j0 == 0, st);       // (the row-major copies of the diagonal blocks: once per call)
         sf::launch_solve_many_unpack(p->d_xm, n, cw, stage, st);
         HIP_TRY(hipEventRecord(e1, st));
         HIP_TRY(hipGetLastError());
