@@ -570,8 +570,8 @@ void launch_trsm(const TrsmTask* tasks, int ntasks, double* Lsx, const int32_t* 
 // ---------------------------------------------------------------------------------------------------
 // fp64 MFMA GEMM  C[ci][cj] -= sum_k Y[ci][k] X[cj][k]   (lower trapezoid ci >= cj)
 //
-// Workgroup = 4 waves (2 x 2), tile 128 (ci) x 128 (cj), K step 16, double-buffered LDS.
-// Each wave owns a 64 x 64 sub-tile = 4 x 4 MFMA tiles of v_mfma_f64_16x16x4_f64:
+// Workgroup = 8 waves (2 x 4), tile 128 (ci) x 128 (cj), K step 16 in two LDS buffers, which the LDS-DMA loop uses as a ring
+// of four 8-deep stages.  Each wave owns a 64 x 32 sub-tile = 4 x 2 MFMA tiles of v_mfma_f64_16x16x4_f64:
 //     A operand (row index of D)  <- X rows (cj)      lane l: X[cj = l&15][k = l>>4]
 //     B operand (col index of D)  <- Y rows (ci)      lane l: Y[ci = l&15][k = l>>4]
 //     D[row = (l>>4) + 4*reg][col = l&15]             (f64 layout: NOT the f32 one)
@@ -581,6 +581,7 @@ void launch_trsm(const TrsmTask* tasks, int ntasks, double* Lsx, const int32_t* 
 // ds_read_b64 fragment reads (16 rows x 2 k per half-wave) hit all 64 banks exactly once.
 // ---------------------------------------------------------------------------------------------------
 constexpr int LDS_LD = GEMM_BM + 16;
+constexpr int GEMM_SK = GEMM_BK / 2;    // depth of one stage of k_gemm's LDS-DMA ring (private to the kernel; a K step is two stages)
 
 // largest i in [0, n) with a[i] <= key   (a ascending, a[0] = 0 <= key)
 __device__ __forceinline__ int last_le_u32(const uint32_t* __restrict__ a, int n, uint32_t key) {
@@ -608,12 +609,14 @@ __device__ double g_zero_page[GEMM_BM + 16];
 // One LDS-DMA of 16 bytes per lane (1 KiB per wave) as inline asm: the builtin form makes hipcc wait vmcnt(0) before the NEXT
 // ds_read (it cannot tell the DMA's LDS destination from the buffer being read), which exposes the whole memory latency once per
 // K step; an asm statement is outside its s_waitcnt bookkeeping, so the DMA stays in flight until the explicit
-// `s_waitcnt vmcnt(0)` in front of the K step's barrier.  (Untracked operations can only make hipcc's own counted waits
+// `s_waitcnt vmcnt(n)` in front of a barrier of the K loop.  (Untracked operations can only make hipcc's own counted waits
 // stricter: vmcnt retires in order.)  M0 = the wave-uniform LDS byte address, saved and restored around the instruction.
-__device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_dst) {
+// The source is a wave-uniform base (scalar registers) plus a 32-bit byte offset per lane: no 64-bit vector address arithmetic
+// and no address registers per staged row.
+__device__ __forceinline__ void glds16(const void* sbase, uint32_t voff, uint32_t lds_dst) {
     unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "s"(sbase), "v"(voff), "s"(lds_dst) : "memory");
 }
 __device__ __forceinline__ uint32_t lds_addr(const void* p) {
     return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p);
@@ -646,6 +649,8 @@ k_gemm(const GemmProb* __restrict__ probs, const GemmTask* __restrict__ tasks,
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;            // wave (wm, wn) owns rows [64 wm, +64) x columns [WCJ wn, +WCJ)
     const int fr = lane & 15, fk = lane >> 4;
+    const int swave = __builtin_amdgcn_readfirstlane(wave);                 // the wave's number in scalar registers (DMA addressing)
+    const uint32_t lds_ys = lds_addr(&Ys[0][0][0]), lds_xs = lds_addr(&Xs[0][0][0]);
 
     // XCD-aware share: workgroups b, b+8, b+16 ... run on one XCD (one L2); give each XCD a contiguous
     // run of shares so that the tiles it works on at any time are neighbours (supertile order).
@@ -776,10 +781,10 @@ k_gemm(const GemmProb* __restrict__ probs, const GemmTask* __restrict__ tasks,
         const bool x0_ok = (cj0 + prow) < N, x1_ok = (cj0 + prow + 1) < N;
         const double* __restrict__ yp = Yg + (y0_ok ? prow : 0);
         const double* __restrict__ xp = Xg + (x0_ok ? prow : 0);
+        const uint32_t yoff = (y0_ok ? prow : 0) * (uint32_t)sizeof(double), xoff = (x0_ok ? prow : 0) * (uint32_t)sizeof(double);
         double2_t ry[DMA ? 1 : SQ], rx[DMA ? 1 : SQ];
 
         auto load_tile = [&](int k0) {
-            if (DMA) return;
 #pragma unroll
             for (int q = 0; q < SQ; ++q) {
                 const int64_t off = (int64_t)min(k0 + pk0 + GEMM_WAVES * q, K - 1) * lda;
@@ -788,19 +793,6 @@ k_gemm(const GemmProb* __restrict__ probs, const GemmTask* __restrict__ tasks,
             }
         };
         auto store_tile = [&](int buf, int k0) {
-            if (DMA) {
-                // wave `pk0` fills k rows pk0 and pk0 + 8 of both operands: four 1 KiB DMAs per K step and wave
-#pragma unroll
-                for (int q = 0; q < SQ; ++q) {
-                    const int kl = pk0 + GEMM_WAVES * q, k = k0 + kl;
-                    const bool kin = k < K;                                     // wave-uniform
-                    const double* ysrc = yp + (int64_t)min(k, K - 1) * lda;
-                    const double* xsrc = kin ? xp + (int64_t)k * lda : g_zero_page + prow;
-                    glds16(ysrc, lds_addr(&Ys[buf][kl][0]));
-                    glds16(xsrc, lds_addr(&Xs[buf][kl][0]));
-                }
-                return;
-            }
 #pragma unroll
             for (int q = 0; q < SQ; ++q) {
                 const bool kin = (k0 + pk0 + GEMM_WAVES * q) < K;
@@ -810,6 +802,24 @@ k_gemm(const GemmProb* __restrict__ probs, const GemmTask* __restrict__ tasks,
                 *reinterpret_cast<double2_t*>(&Ys[buf][pk0 + GEMM_WAVES * q][prow]) = vy;
                 *reinterpret_cast<double2_t*>(&Xs[buf][pk0 + GEMM_WAVES * q][prow]) = vx;
             }
+        };
+        // DMA: one ring stage = GEMM_SK k rows = half a K step; wave `pk0` fills row pk0 of both operands (two 1 KiB DMAs per
+        // stage and wave).  Stage (K step kt, half h) lives in rows [GEMM_SK h, +GEMM_SK) of buffer (kt - kt0) & 1.
+        auto dma_stage = [&](int buf, int half, int kt) {
+            const int kl = half * GEMM_SK + swave, k = kt * GEMM_BK + kl;
+            const uint32_t slot = (uint32_t)((buf * GEMM_BK + kl) * LDS_LD) * (uint32_t)sizeof(double);
+            const bool kin = k < K;                                     // wave-uniform, as are both source rows
+            const double* ysrc = Yg + (int64_t)min(k, K - 1) * lda;
+            const double* xsrc = kin ? Xg + (int64_t)k * lda : g_zero_page;
+            glds16(ysrc, yoff, lds_ys + slot);
+            glds16(xsrc, xoff, lds_xs + slot);
+        };
+        // the MFMA fragments of the 4-deep k group that starts at row `krow` of buffer `buf`
+        auto read_frag = [&](double (&a)[TMN], double (&b)[4], int buf, int krow) {
+#pragma unroll
+            for (int t = 0; t < TMN; ++t) a[t] = Xs[buf][krow + fk][wn * WCJ + t * 16 + fr];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) b[t] = Ys[buf][krow + fk][wm * 64 + t * 16 + fr];
         };
 
         // a wave whose 64x64 quadrant lies entirely outside the lower trapezoid does no MFMA work
@@ -823,12 +833,80 @@ k_gemm(const GemmProb* __restrict__ probs, const GemmTask* __restrict__ tasks,
 #pragma unroll
             for (int b = 0; b < 4; ++b) acc[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
 
-        // Software pipeline, one barrier per K step: while step kt is multiplied out of LDS buffer `buf`, the
-        // registers holding step kt+1 are written to the other buffer and re-filled with step kt+2 -- both in
+        auto mma = [&](const double (&a)[TMN], const double (&b)[4]) {
+#pragma unroll
+            for (int tm = 0; tm < TMN; ++tm)
+#pragma unroll
+                for (int tn = 0; tn < 4; ++tn)
+                    acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
+        };
+
+        if constexpr (DMA) {
+        // Software pipeline over a RING OF FOUR 8-deep stages (the two 16-deep buffers, each cut in halves), one barrier per
+        // stage.  While stage s is multiplied, stage s+1 is complete in LDS, stage s+2 is landing and the DMAs of stage s+3 are
+        // issued into the slot stage s-1 was read from.  The wait in front of the barrier that ends stage s is for this wave's
+        // DMAs of stage s+2 only (vmcnt retires in order: the two DMAs of stage s+3 may stay in flight), so a DMA has two stage
+        // times to land.  Because stage s+1 is visible to every wave before that barrier, the fragments of its first k group are
+        // read during the last k group of stage s into a second set of fragment registers: the first MFMAs behind a barrier
+        // issue without an LDS round trip.  The one barrier covers both hazards: every wave is done reading the slot that is
+        // overwritten next, and every wave's DMAs into the stage after the next have landed.  k is accumulated in the same
+        // order as by a 16-deep loop.  Nothing is staged beyond K step kt1 - 1: the wait is vmcnt(0) where nothing was issued.
+        dma_stage(0, 0, kt0);
+        dma_stage(0, 1, kt0);
+        if (kt0 + 1 < kt1) {
+            dma_stage(1, 0, kt0 + 1);
+            asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __syncthreads();                    // stages 0 and 1 are complete
+        SF_STAMP(1);
+        // (the K steps are taken in pairs so that the buffer of every LDS access is a compile-time constant: all fragment reads
+        //  are one base register per operand plus an immediate offset)
+        if (quad_active) {
+            double a0[TMN], b0[4], a1[TMN], b1[4];
+            read_frag(a0, b0, 0, 0);
+            auto k_step = [&](const int buf, int kt) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const bool more = kt + 1 + h < kt1;
+                    read_frag(a1, b1, buf, h * GEMM_SK + 4);
+                    if (more) dma_stage(h ? buf : buf ^ 1, h ^ 1, kt + 1 + h);      // stage s+3
+                    mma(a0, b0);
+                    read_frag(a0, b0, h ? buf ^ 1 : buf, h ? 0 : GEMM_SK);         // first k group of stage s+1
+                    mma(a1, b1);
+                    if (more) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");     // stage s+2 has landed
+                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __syncthreads();
+                }
+            };
+            int kt = kt0;
+            for (; kt + 1 < kt1; kt += 2) {
+                k_step(0, kt);
+                k_step(1, kt + 1);
+            }
+            if (kt < kt1) k_step(0, kt);
+        } else {
+            for (int kt = kt0; kt < kt1; ++kt) {     // staging only, same barriers
+                const int buf = (kt - kt0) & 1;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    if (kt + 1 + h < kt1) {
+                        dma_stage(h ? buf : buf ^ 1, h ^ 1, kt + 1 + h);
+                        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+                    } else {
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    }
+                    __syncthreads();
+                }
+            }
+        }
+        } else {
+        // Register staging, software pipeline with one barrier per K step: while step kt is multiplied out of LDS buffer `buf`,
+        // the registers holding step kt+1 are written to the other buffer and re-filled with step kt+2 -- both in
         // the shadow of this wave's own MFMAs (an MFMA occupies the matrix pipe for 64 cycles after it issues).
         load_tile(kt0 * GEMM_BK);
         store_tile(0, kt0 * GEMM_BK);
-        if (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         SF_STAMP(1);
         load_tile((kt0 + 1) * GEMM_BK);
@@ -838,19 +916,11 @@ k_gemm(const GemmProb* __restrict__ probs, const GemmTask* __restrict__ tasks,
 #pragma unroll
                 for (int kk = 0; kk < GEMM_BK / 4; ++kk) {
                     double a[TMN], b[4];
-#pragma unroll
-                    for (int t = 0; t < TMN; ++t) a[t] = Xs[buf][kk * 4 + fk][wn * WCJ + t * 16 + fr];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) b[t] = Ys[buf][kk * 4 + fk][wm * 64 + t * 16 + fr];
+                    read_frag(a, b, buf, kk * 4);
                     if (kk == 0) store_tile(buf ^ 1, (kt + 1) * GEMM_BK);
                     if (kk == 1) load_tile((kt + 2) * GEMM_BK);
-#pragma unroll
-                    for (int tm = 0; tm < TMN; ++tm)
-#pragma unroll
-                        for (int tn = 0; tn < 4; ++tn)
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
+                    mma(a, b);
                 }
-                if (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the next K step's tile has landed
                 __syncthreads();
                 buf ^= 1;
             }
@@ -858,10 +928,10 @@ k_gemm(const GemmProb* __restrict__ probs, const GemmTask* __restrict__ tasks,
             for (int kt = kt0; kt < kt1; ++kt) {     // staging only, same barriers
                 store_tile(buf ^ 1, (kt + 1) * GEMM_BK);
                 load_tile((kt + 2) * GEMM_BK);
-                if (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
                 buf ^= 1;
             }
+        }
         }
 
         SF_STAMP(2);
