@@ -402,6 +402,27 @@ int sf_lu_plan_residual(sf_lu_plan *plan, const sf_float *b_host, const sf_float
                         sf_float *r_host /* or NULL */, sf_float *berr /* or NULL */, sf_float *nerr /* or NULL */);
 int sf_lu_plan_refine(sf_lu_plan *plan, const sf_float *b_host, sf_float *x_host,
                       int max_iter, double tol, sf_float *berr /* or NULL */);
+/* selected inversion of an LU plan: Sigma = A^{-1} = (L U)^{-1} on the pattern of L + U, permuted space, into a plan-owned pair of
+ * device arenas with the device factor's layout.  Synchronous.  Arenas and scratch are allocated by the first call
+ * and kept until destroy (stat "bytes_selinv", not in "bytes_device"); SF_ERR_ALLOC leaves the plan usable.  Needs a successful
+ * factorization of the current values; whole, resident LU plans only, U aliasing L included (schedule-only, partial, sharded,
+ * mapped, out-of-core and Cholesky plans: SF_ERR_ARG).  A plan whose pivot threshold tol is > 0 is refused too (SF_ERR_ARG): the
+ * in-block interchanges leave the L entries left of a block in their old rows, so the stored panels are not factors of one
+ * row-permuted A.  perturb > 0 with tol == 0 is accepted: Sigma is then the inverse of the perturbed factorization L U, not of A
+ * ("perturbed_pivots" tells).  Stats as for sf_chol_plan_selinv: "last_selinv_ms", "flops_selinv", "selinv_valid". */
+int sf_lu_plan_selinv(sf_lu_plan *plan);
+/* values [e_begin, e_end) of Sigma in the layout of sf_lu_plan_get_factor (xsize doubles, panel s at Lsxp[s],
+ * (2*nsrow-nscol) x nscol column-major): rows [0,nscol) the full block Sigma(C_s,C_s), [nscol,nsrow) Sigma(R,C_s),
+ * [nsrow,2*nsrow-nscol) Sigma(C_s,R)^T.  SF_ERR_ARG when the arena is not valid. */
+int sf_lu_plan_get_selinv_range(sf_lu_plan *plan, sf_long e_begin, sf_long e_end, sf_float *out);
+/* diag(Sigma), n doubles, gathered on the device (SF_ERR_ARG when the arena is not valid) */
+int sf_lu_plan_selinv_diag(sf_lu_plan *plan, sf_float *d);
+/* log|det A| = sum_j log|U_jj| of the resident factor, reduced on the device in a fixed order, and (sign may be NULL) the sign of
+ * det A = (-1)^(number of negative U_jj) x the parity of the plan's row interchanges.  Independent of selinv and allowed with
+ * pivoting on (the pivot policy must be the one the resident factor was computed with, as for the solves); otherwise refused for the
+ * same plan kinds.  Needs a successful factorization of the current values.  In permuted space, which has the determinant of the
+ * caller's matrix: the ordering is applied to rows and columns alike. */
+int sf_lu_plan_logdet(sf_lu_plan *plan, sf_float *logabs, int *sign);
 double sf_lu_plan_stat(const sf_lu_plan *plan, const char *name);
 int sf_lu_plan_set_profiling(sf_lu_plan *plan, int on);
 int sf_lu_plan_destroy(sf_lu_plan *plan);

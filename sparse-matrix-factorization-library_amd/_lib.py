@@ -239,6 +239,14 @@ lib.sf_lu_plan_solve.argtypes = [C.c_void_p, c_double_p, c_double_p]
 lib.sf_lu_plan_solve.restype = C.c_int
 lib.sf_lu_plan_solve_many.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64]
 lib.sf_lu_plan_solve_many.restype = C.c_int
+lib.sf_lu_plan_selinv.argtypes = [C.c_void_p]
+lib.sf_lu_plan_selinv.restype = C.c_int
+lib.sf_lu_plan_get_selinv_range.argtypes = [C.c_void_p, C.c_int64, C.c_int64, c_double_p]
+lib.sf_lu_plan_get_selinv_range.restype = C.c_int
+lib.sf_lu_plan_selinv_diag.argtypes = [C.c_void_p, c_double_p]
+lib.sf_lu_plan_selinv_diag.restype = C.c_int
+lib.sf_lu_plan_logdet.argtypes = [C.c_void_p, c_double_p, C.POINTER(C.c_int)]
+lib.sf_lu_plan_logdet.restype = C.c_int
 lib.sf_lu_plan_stat.argtypes = [C.c_void_p, C.c_char_p]
 lib.sf_lu_plan_stat.restype = C.c_double
 lib.sf_lu_plan_set_profiling.argtypes = [C.c_void_p, C.c_int]

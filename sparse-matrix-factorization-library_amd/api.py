@@ -646,6 +646,31 @@ class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin):
         """X = A^-1 B for an (n, k) block of right-hand sides (any memory order), permuted space, 16 columns per device sweep"""
         return _solve_many(lib.sf_lu_plan_solve_many, "sf_lu_plan_solve_many", self._h, self.n, B)
 
+    def selinv(self):
+        """selected inversion: A^-1 on the pattern of L + U into a pair of device arenas (permuted space), from the resident
+        factor; refused while threshold pivoting is on"""
+        check(lib.sf_lu_plan_selinv(self._h), "sf_lu_plan_selinv")
+
+    def get_selinv(self, out=None):
+        """D2H of the selected inverse in get_factor's packed layout: per panel the full diagonal block, Sigma(R,C), Sigma(C,R)^T"""
+        if out is None:
+            out = np.zeros(max(self.xsize, 1), dtype=np.float64)
+        check(lib.sf_lu_plan_get_selinv_range(self._h, 0, self.xsize, _dp(out)), "sf_lu_plan_get_selinv_range")
+        return out[:self.xsize]
+
+    def selinv_diag(self):
+        """diag(A^-1), permuted space, gathered on the device"""
+        d = np.zeros(max(self.n, 1), dtype=np.float64)
+        check(lib.sf_lu_plan_selinv_diag(self._h, _dp(d)), "sf_lu_plan_selinv_diag")
+        return d[:self.n]
+
+    def logdet(self):
+        """(log|det A|, sign of det A) from the U diagonal of the resident factor and the parity of its row interchanges"""
+        out = np.zeros(1, dtype=np.float64)
+        sign = C.c_int(0)
+        check(lib.sf_lu_plan_logdet(self._h, _dp(out), C.byref(sign)), "sf_lu_plan_logdet")
+        return float(out[0]), int(sign.value)
+
     def stat(self, name):
         return float(lib.sf_lu_plan_stat(self._h, name.encode()))
 

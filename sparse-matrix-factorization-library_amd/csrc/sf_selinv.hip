@@ -14,7 +14,7 @@
 //
 //   k_selinv_small  : one workgroup per narrow supernode (nscol <= SEL_SMALL_W, short R), the whole supernode as one unit
 //   k_selinv_trinv  : Linv of one unit, one workgroup per column
-//   k_selinv_gemm   : fp64 MFMA (v_mfma_f64_16x16x4_f64) C = op(A) B, 64 x 64 tiles; A plain, transposed or the gathered
+//   k_selinv_gemm   : (sf_selinv_common.h, shared with the LU selected inversion) fp64 MFMA (v_mfma_f64_16x16x4_f64) C = op(A) B, 64 x 64 tiles; A plain, transposed or the gathered
 //                     Sigma(R,R); optional split of K into slabs (no atomics: the slabs are summed in a fixed order)
 //   k_selinv_sum    : the fixed-order slab sum
 //   k_selinv_finish : Sigma(R,C) = -Z (with the mirror for R rows inside J) and Sigma(C,C) with its mirror
@@ -28,44 +28,9 @@
 #include <string>
 #include <vector>
 
-#include "sf_plan_internal.h"
+#include "sf_selinv_common.h"
 
 namespace sf {
-
-typedef double double4_v __attribute__((ext_vector_type(4)));
-
-// panel position q of J (q >= the unit's first R position) as the column of a Sigma(hi, q) read: base offset of the column in the
-// arena and the relative-map offset that turns the panel position hi of J into a row position of that column's panel (SEL_OWN: J's
-// own column, the row position is hi itself; a real offset map_off - i can be negative)
-struct SelCol { int64_t base; int64_t moff; };
-constexpr int64_t SEL_OWN = INT64_MIN;
-
-__device__ __forceinline__ SelCol sel_col(const SelUnit& u, int q, const int32_t* __restrict__ Super, const int32_t* __restrict__ SuperMap,
-                                          const int64_t* __restrict__ Lsip, const int32_t* __restrict__ Lsi, const int64_t* __restrict__ Lsxp,
-                                          const SelPair* __restrict__ pairs) {
-    SelCol c;
-    if (q < u.ncol) {
-        c.base = u.lx + (int64_t)q * u.nsrow;
-        c.moff = SEL_OWN;
-        return c;
-    }
-    // the scatter problem (J, a) whose rows start at the last pair start <= q
-    int lo = 0, hi = u.npair - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pairs[u.pair0 + mid].i <= q) lo = mid; else hi = mid - 1;
-    }
-    const SelPair pr = pairs[u.pair0 + lo];
-    const int32_t g = Lsi[u.rows + q];
-    const int32_t a = SuperMap[g];
-    c.base = Lsxp[a] + (int64_t)(g - Super[a]) * (Lsip[a + 1] - Lsip[a]);
-    c.moff = pr.map_off - pr.i;
-    return c;
-}
-
-__device__ __forceinline__ double sel_at(const SelCol& c, int hi, const int32_t* __restrict__ relmap, const double* __restrict__ S) {
-    return S[c.base + (c.moff == SEL_OWN ? (int64_t)hi : (int64_t)relmap[c.moff + hi])];
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // narrow supernodes: one workgroup does the whole supernode (cb = 0, w = nscol <= SEL_SMALL_W, R = its below rows) in LDS
@@ -157,96 +122,6 @@ k_selinv_trinv(SelUnit u, const double* __restrict__ Lsx, double* __restrict__ L
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// C (M x N, leading dimension ldc) = op(A) B (+ C when acc), B column-major K x N (ldb).  AM = 0: A column-major M x K (lda);
-// AM = 1: A = X^T with X column-major K x M (lda); AM = 2: A = Sigma(R,R) of unit u, gathered (M = K = |R|).  Workgroup
-// (bx, by, z): the 64 x 64 tile (bx, by) over the K slab [z kslab, (z + 1) kslab), written to C + z cstride.  Four waves
-// (2 x 2), each a 32 x 32 sub-tile = 2 x 2 v_mfma_f64_16x16x4_f64 tiles; 16-deep K chunks staged in LDS.
-// ---------------------------------------------------------------------------------------------------------------------------
-constexpr int SG_T = 64, SG_K = 16, SG_LD = SG_T + 4;
-
-template <int AM>
-__global__ void __launch_bounds__(256)
-k_selinv_gemm(int M, int N, int K, const double* __restrict__ A, int64_t lda, const double* __restrict__ B, int64_t ldb,
-              double* __restrict__ C, int64_t ldc, int kslab, int64_t cstride, int acc_in, SelUnit u, const double* __restrict__ S,
-              const int32_t* __restrict__ Super, const int32_t* __restrict__ SuperMap, const int64_t* __restrict__ Lsip,
-              const int32_t* __restrict__ Lsi, const int64_t* __restrict__ Lsxp, const SelPair* __restrict__ pairs,
-              const int32_t* __restrict__ relmap) {
-    __shared__ __attribute__((aligned(16))) double As[SG_K][SG_LD];
-    __shared__ __attribute__((aligned(16))) double Bs[SG_K][SG_LD];
-    __shared__ int64_t rbase[SG_T], rmoff[SG_T], kbase[SG_K], kmoff[SG_K];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave & 1, wn = wave >> 1, fr = lane & 15, fk = lane >> 4;
-    const int m0 = blockIdx.x * SG_T, n0 = blockIdx.y * SG_T;
-    const int k0 = blockIdx.z * kslab, k1 = min(K, k0 + kslab);
-    C += (int64_t)blockIdx.z * cstride;
-    const int ce = u.cb + u.w;
-    if (AM == 2 && tid < SG_T && m0 + tid < M) {
-        const SelCol c = sel_col(u, ce + m0 + tid, Super, SuperMap, Lsip, Lsi, Lsxp, pairs);
-        rbase[tid] = c.base;
-        rmoff[tid] = c.moff;
-    }
-    double4_v acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = (double4_v){0.0, 0.0, 0.0, 0.0};
-    for (int kc = k0; kc < k1; kc += SG_K) {
-        __syncthreads();            // the previous chunk's reads are done (and, AM == 2, the row columns are in place)
-        if (AM == 2 && tid < SG_K && kc + tid < k1) {
-            const SelCol c = sel_col(u, ce + kc + tid, Super, SuperMap, Lsip, Lsi, Lsxp, pairs);
-            kbase[tid] = c.base;
-            kmoff[tid] = c.moff;
-        }
-        if (AM == 2) __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int e = tid + 256 * r;
-            int row, kk;
-            if (AM == 1) { kk = e & 15; row = e >> 4; } else { row = e & 63; kk = e >> 6; }
-            const int gi = m0 + row, gk = kc + kk;
-            double v = 0.0;
-            if (gi < M && gk < k1) {
-                if (AM == 0) v = A[gi + (int64_t)gk * lda];
-                else if (AM == 1) v = A[gk + (int64_t)gi * lda];
-                else v = (gi >= gk) ? sel_at(SelCol{kbase[kk], kmoff[kk]}, ce + gi, relmap, S)
-                                    : sel_at(SelCol{rbase[row], rmoff[row]}, ce + gk, relmap, S);
-            }
-            As[kk][row] = v;
-            const int bk = e & 15, bn = e >> 4;
-            const int gn = n0 + bn, gbk = kc + bk;
-            Bs[bk][bn] = (gn < N && gbk < k1) ? B[gbk + (int64_t)gn * ldb] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < SG_K / 4; ++s) {
-            double a[2], b[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                a[t] = As[4 * s + fk][32 * wm + 16 * t + fr];
-                b[t] = Bs[4 * s + fk][32 * wn + 16 * t + fr];
-            }
-#pragma unroll
-            for (int ta = 0; ta < 2; ++ta)
-#pragma unroll
-                for (int tb = 0; tb < 2; ++tb) acc[ta][tb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ta], b[tb], acc[ta][tb], 0, 0, 0);
-        }
-    }
-    // D fragment: column lane & 15 (B side), rows (lane >> 4) + 4 r (A side)
-#pragma unroll
-    for (int ta = 0; ta < 2; ++ta)
-#pragma unroll
-        for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int gi = m0 + 32 * wm + 16 * ta + fk + 4 * r, gn = n0 + 32 * wn + 16 * tb + fr;
-                if (gi < M && gn < N) {
-                    double* cp = C + gi + (int64_t)gn * ldc;
-                    *cp = acc_in ? *cp + acc[ta][tb][r] : acc[ta][tb][r];
-                }
-            }
-}
-
 // dst[e] (+)= sum_{z < nslab} src[z * stride + e], z in increasing order
 __global__ void __launch_bounds__(256)
 k_selinv_sum(const double* __restrict__ src, int nslab, int64_t stride, int64_t count, double* __restrict__ dst, int acc_in) {
@@ -335,12 +210,6 @@ bool selinv_refused(const sf_chol_plan* p) {
     return p->dry || p->lu || p->partial || p->nranks > 1 || p->ooc_groups > 1 || (p->nsuper > 0 && !p->d_solve);
 }
 
-// a successful factorization of the plan's current values is on the device (a finished but unsynchronised one is collected here)
-bool factor_current(sf_chol_plan* p) {
-    if (p->ok_gen != p->factor_gen && p->fact_gen == p->factor_gen) (void)sf_chol_plan_sync(p);
-    return p->ok_gen == p->factor_gen;
-}
-
 int64_t slabs_for(int64_t tiles, int64_t K) {
     if (tiles <= 0 || tiles >= 256 || K < 512) return 1;         // (a unit with no rows below: no product at all)
     return std::max<int64_t>(1, std::min<int64_t>({sf::SEL_MAX_SLABS, (256 + tiles - 1) / tiles, K / 256}));
@@ -348,11 +217,18 @@ int64_t slabs_for(int64_t tiles, int64_t K) {
 
 double unit_flops(double m, double w) { return 2.0 * m * m * w + 2.0 * m * w * w + 2.0 / 3.0 * w * w * w; }
 
-// the schedule (first call): units, pair table on the device, scratch sizes
-int selinv_schedule(sf_chol_plan* p) {
+}  // namespace
+
+bool sf_selinv_factor_current(sf_chol_plan* p) {
+    if (p->ok_gen != p->factor_gen && p->fact_gen == p->factor_gen) (void)sf_chol_plan_sync(p);
+    return p->ok_gen == p->factor_gen;
+}
+
+int sf_selinv_schedule(sf_chol_plan* p) {
     const int64_t ns = p->nsuper;
     const std::vector<int64_t>& Lsip = p->h_Lsip;
-    const std::vector<int64_t>& Lsxp = p->h_Lsxp;
+    const std::vector<int64_t>& Lsxp = p->lu ? p->h_XP : p->h_Lsxp;      // the panels' offsets on the device
+    const double sides = p->lu ? 2.0 : 1.0;                              // LU: every product of a unit once per panel set
     const std::vector<int32_t>& Super = p->h_Super;
     // (J, a) -> map_off, bucketed by J (recorded in enumeration order while plan_create built the scatter problems)
     std::vector<int32_t> pf(ns + 1, 0);
@@ -389,7 +265,7 @@ int selinv_schedule(sf_chol_plan* p) {
             if (u.ncol <= sf::SEL_SMALL_W && mb <= sf::SEL_SMALL_M && mb * u.ncol <= sf::SEL_SMALL_Y) {
                 u.cb = 0; u.w = u.ncol;
                 p->sel_small.push_back(u);
-                p->flops_selinv += unit_flops((double)mb, (double)u.w);
+                p->flops_selinv += sides * unit_flops((double)mb, (double)u.w);
                 continue;
             }
             for (int cb = ((u.ncol - 1) / sf::SEL_UW) * sf::SEL_UW; cb >= 0; cb -= sf::SEL_UW) {
@@ -403,7 +279,7 @@ int selinv_schedule(sf_chol_plan* p) {
                 ysz = std::max(ysz, m * w);
                 zsl = std::max(zsl, (int64_t)b.zslabs * m * w);
                 ssl = std::max(ssl, (int64_t)b.sslabs * w * w);
-                p->flops_selinv += unit_flops((double)m, (double)w);
+                p->flops_selinv += sides * unit_flops((double)m, (double)w);
             }
         }
         // one step per level: the level's big units (in list order), then its narrow supernodes in one launch
@@ -418,6 +294,13 @@ int selinv_schedule(sf_chol_plan* p) {
     p->sel_scheduled = true;
     return SF_OK;
 }
+
+void sf_selinv_slab_sum(const double* src, int nslab, int64_t count, double* dst, int acc_in, hipStream_t st) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(sf::k_selinv_sum, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, src, nslab, count, count, dst, acc_in);
+}
+
+namespace {
 
 // arena + scratch; on failure everything allocated here is released and the plan is as before
 int selinv_alloc(sf_chol_plan* p) {
@@ -451,17 +334,7 @@ int selinv_alloc(sf_chol_plan* p) {
 template <int AM>
 void gemm(sf_chol_plan* p, int M, int N, int K, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
           int slabs, int64_t cstride, int acc_in, const SelUnit& u, hipStream_t st) {
-    if (M <= 0 || N <= 0) return;
-    const int kslab = ((K + slabs - 1) / slabs + sf::SG_K - 1) / sf::SG_K * sf::SG_K;
-    const dim3 grid((M + 63) / 64, (N + 63) / 64, slabs);
-    hipLaunchKernelGGL(sf::k_selinv_gemm<AM>, grid, dim3(256), 0, st, M, N, K, A, lda, B, ldb, C, ldc, kslab, cstride, acc_in, u,
-                       (const double*)p->d_sel, p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, p->d_Lsxp,
-                       (const sf::SelPair*)p->d_sel_pairs, p->d_relmap);
-}
-
-void slab_sum(const double* src, int nslab, int64_t count, double* dst, int acc_in, hipStream_t st) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL(sf::k_selinv_sum, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, src, nslab, count, count, dst, acc_in);
+    sf::selinv_gemm<AM>(p, M, N, K, A, lda, B, ldb, C, ldc, slabs, cstride, acc_in, u, sf::SelArenas{p->d_sel, p->d_sel, p->d_Lsxp}, st);
 }
 
 // one unit of a wide or long supernode
@@ -484,13 +357,13 @@ void run_big(sf_chol_plan* p, const sf_chol_plan::SelBig& b, hipStream_t st) {
             gemm<2>(p, m, w, m, nullptr, 0, Y, m, Zs, m, 1, 0, 0, u, st);                                               // Z = Sigma(R,R) Y
         } else {
             gemm<2>(p, m, w, m, nullptr, 0, Y, m, Zsl, m, b.zslabs, (int64_t)m * w, 0, u, st);
-            slab_sum(Zsl, b.zslabs, (int64_t)m * w, Zs, 0, st);
+            sf_selinv_slab_sum(Zsl, b.zslabs, (int64_t)m * w, Zs, 0, st);
         }
         if (b.sslabs == 1) {
             gemm<1>(p, w, w, m, Y, m, Zs, m, Sc, w, 1, 0, 1, u, st);                                                      // Sc += Y^T Z
         } else {
             gemm<1>(p, w, w, m, Y, m, Zs, m, Ssl, w, b.sslabs, (int64_t)w * w, 0, u, st);
-            slab_sum(Ssl, b.sslabs, (int64_t)w * w, Sc, 1, st);
+            sf_selinv_slab_sum(Ssl, b.sslabs, (int64_t)w * w, Sc, 1, st);
         }
     }
     const int64_t tot = (int64_t)m * w + (int64_t)w * w;
@@ -504,11 +377,11 @@ extern "C" {
 
 int sf_chol_plan_selinv(sf_chol_plan* p) {
     if (!p || selinv_refused(p)) return SF_ERR_ARG;
-    if (!factor_current(p)) return SF_ERR_ARG;
+    if (!sf_selinv_factor_current(p)) return SF_ERR_ARG;
     if (p->n <= 0) return SF_OK;
     HIP_TRY(hipSetDevice(p->device));
     if (!p->sel_scheduled) {
-        const int rc = selinv_schedule(p);
+        const int rc = sf_selinv_schedule(p);
         if (rc) return rc;
     }
     {
@@ -560,7 +433,7 @@ int sf_chol_plan_selinv_diag(sf_chol_plan* p, sf_float* d) {
 
 int sf_chol_plan_logdet(sf_chol_plan* p, sf_float* out) {
     if (!p || !out || selinv_refused(p)) return SF_ERR_ARG;
-    if (!factor_current(p)) return SF_ERR_ARG;
+    if (!sf_selinv_factor_current(p)) return SF_ERR_ARG;
     *out = 0.0;
     if (p->n <= 0) return SF_OK;
     HIP_TRY(hipSetDevice(p->device));
