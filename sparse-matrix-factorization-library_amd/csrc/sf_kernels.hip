@@ -254,7 +254,7 @@ __device__ __forceinline__ void getrf_panel_wave(double (&a)[W], int lane, int J
             ++nperturbed;
             if (lane == p) a[j] = piv;
         }
-        bad = bad || !(piv != 0.0);             // zero or NaN pivot; padded rows have piv = 1
+        bad = bad || !(fabs(piv) > 0.0);        // zero or NaN pivot (NaN != 0.0 is true); padded rows have piv = 1
         const bool elim = active && lane != p;
         double l;
         if (RCP) {

@@ -7,6 +7,7 @@ rounding is far below the bounds.  Every bound is per ELEMENT, of the form the a
     POTRF          |A - L^ L^T|   <= SAFETY (b + 2) u |L^| |L^T|
     GETRF          |PA - L^ U^|   <= SAFETY (b + 2) u |L^| |U^|
     TRSM           |X^ D^T - B|   <= SAFETY (b + 2) u |X^| |D^T|
+    LU panel       |A - L~ U~|    <= SAFETY (terms + 2) u |L~| |U~|      (fused steps, from the stored factor: lu_panel_check)
     solve sweeps   |sum of an equation's terms - its right-hand side| <= SAFETY (terms) u (sum of the terms' magnitudes)
 A max-normalised metric (max error / max |ref|) would hide an error in a row scaled by 1e-6; these do not.
 
@@ -183,3 +184,111 @@ def assert_equations(total, rhs, nterms, mag, cols, what):
         k = tuple(np.argwhere(viol)[0])
         raise AssertionError(f"{what}: {int(viol.sum())} of {viol.size} equations beyond the bound, first at {list(k)} "
                              f"(err {float(err[k]):.3e}, bound {float(bound[k]):.3e})")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# LU panels factored by fused 64-column steps (k_step<true>): tests/test_kernels_lu.py
+# ---------------------------------------------------------------------------------------------------------------------
+LU_NB = 64
+
+
+def _solve_right_upper(B, Uu):
+    """X with X Uu = B (Uu upper triangular), longdouble, column by column"""
+    X = np.array(B, dtype=LD)
+    for c in range(Uu.shape[0]):
+        X[:, c] = (X[:, c] - X[:, :c] @ Uu[:c, c]) / Uu[c, c]
+    return X
+
+
+def _solve_left_unit_lower(L, B):
+    """Y with L Y = B (L unit lower triangular), longdouble, row by row"""
+    Y = np.array(B, dtype=LD)
+    for r in range(1, L.shape[0]):
+        Y[r] -= L[r, :r] @ Y[:r]
+    return Y
+
+
+def lu_full(A11, A21, A12):
+    """the panel's matrix [[A11, A12], [A21, nan]] with its rows and columns in original order (the corner is never formed)"""
+    nscol, below = A11.shape[0], A21.shape[0]
+    A = np.full((nscol + below, nscol + below), np.nan)
+    A[:nscol, :nscol], A[nscol:, :nscol], A[:nscol, nscol:] = A11, A21, A12
+    return A
+
+
+def lu_panel_ref(A11, A21, A12, tol, eps, J=0):
+    """longdouble restatement of what the fused LU steps of one panel compute from column J on (sf_plan_build.hip, fused_step;
+    sf_kernels.h, PivotCtl).  For each 64-column block in turn: the block, the rows below it and the columns to its right are
+    updated with all earlier blocks (L rows in ORIGINAL order: interchanges stay inside a block), getrf_rule factors the
+    diagonal block, then L21 = A21' U11^-1 and U12 = L11^-1 P A12'.
+    Returns (pos, PL, PU, perturbed, margin): pos[r] = position of original row r (identity before J); PL / PU = the factor as
+    the device stores it, nsrow x nscol each (L strictly lower, U^T lower with the diagonal; what no task writes is NaN);
+    perturbed = the panel columns whose pivot was replaced; margin = the smallest decision margin over all blocks."""
+    nscol, below = A11.shape[0], A21.shape[0]
+    nsrow = nscol + below
+    A = lu_full(A11, A21, A12).astype(LD)
+    PL = np.full((nsrow, nscol), np.nan, dtype=LD)
+    PU = np.full((nsrow, nscol), np.nan, dtype=LD)
+    pos = np.arange(nscol)
+    perturbed, margin = [], np.inf
+    for c0 in range(J, nscol, LU_NB):
+        c1 = min(c0 + LU_NB, nscol)
+        b = c1 - c0
+        S = A[c0:, c0:c1] - matmul_ld(PL[c0:, J:c0], PU[c0:c1, J:c0].T)       # rows c0.. of the block's columns
+        T = A[c0:c1, c1:] - matmul_ld(PL[c0:c1, J:c0], PU[c1:, J:c0].T)       # the block's rows of the columns to its right
+        p, L, Uu, pert, m = getrf_rule(S[:b], tol, eps)
+        row_at = np.argsort(p)
+        pos[c0:c1] = c0 + p
+        perturbed += [c0 + j for j in pert]
+        margin = min(margin, m)
+        lo = np.tril(np.ones((b, b), dtype=bool), -1)
+        PL[c0:c1, c0:c1][lo] = L[lo]
+        PU[c0:c1, c0:c1][~lo.T] = Uu.T[~lo.T]
+        PL[c1:, c0:c1] = _solve_right_upper(S[b:], Uu)
+        PU[c1:, c0:c1] = _solve_left_unit_lower(L, T[row_at]).T
+    return pos, PL, PU, perturbed, margin
+
+
+def lu_panel_check(A11, A21, A12, PL, PU, pos, perturbed, J, what):
+    """The STORED factor (PL, PU: nsrow x nscol, fp64, as the device leaves them) against the panel's matrix, element by element, no
+    reference factor needed.  With L~ = the stored L rows put back in original row order inside their own block (unit diagonal
+    added; entries left of the block are stored in original order already) and U~(i, c) = PU(c, i), c >= i:
+        A(r, c) = sum_i L~(r, i) U~(i, c)       for every (r, c) outside the (below x below) corner,
+        |A - L~ U~|(r, c) <= SAFETY (terms + 2) u (|L~| |U~|)(r, c),   terms = min(end of r's block, c + 1) - J,
+    i.e. the number of products the sum can hold.  The diagonal entry of a perturbed column is exempt.  Returns the worst
+    err / bound over the checked elements."""
+    nscol, below = A11.shape[0], A21.shape[0]
+    nsrow = nscol + below
+    n = nscol - J
+    A = lu_full(A11, A21, A12)[J:, J:].astype(LD)
+    PL, PU = np.asarray(PL)[J:, J:], np.asarray(PU)[J:, J:]
+    Lt = np.zeros((nsrow - J, n), dtype=LD)
+    Ut = np.zeros((n, nsrow - J), dtype=LD)
+    limit = np.full(nsrow - J, n)
+    for c0 in range(0, n, LU_NB):
+        c1 = min(c0 + LU_NB, n)
+        b = c1 - c0
+        p = np.asarray(pos[J + c0:J + c1]) - (J + c0)
+        assert sorted(p.tolist()) == list(range(b)), f"{what}: pos is no permutation inside the block at column {J + c0}"
+        Lt[c0:c1, :c0] = PL[c0:c1, :c0]
+        Lt[c0:c1, c0:c1] = (np.tril(PL[c0:c1, c0:c1], -1) + np.eye(b))[p]
+        Lt[c1:, c0:c1] = PL[c1:, c0:c1]
+        Ut[c0:c1, c0:c1] = np.triu(PU[c0:c1, c0:c1].T)
+        Ut[c0:c1, c1:] = PU[c1:, c0:c1].T
+        limit[c0:c1] = c1
+    if not (np.all(np.isfinite(Lt)) and np.all(np.isfinite(Ut))):
+        raise AssertionError(f"{what}: non-finite stored factor entries")
+    terms = np.minimum(limit[:, None], np.arange(nsrow - J)[None, :] + 1)
+    mag = matmul_ld(np.abs(Lt), np.abs(Ut))
+    err = np.abs(A - matmul_ld(Lt, Ut))
+    bound = SAFETY * (terms + 2) * U * mag
+    check = np.ones(A.shape, dtype=bool)
+    check[n:, n:] = False
+    for j in perturbed:                     # the factorization is of A + E, E on the replaced pivot
+        check[np.flatnonzero(np.asarray(pos[J:]) == j)[0], j - J] = False
+    viol = check & ~(err <= bound)
+    if viol.any():
+        k = tuple(np.argwhere(viol)[0])
+        raise AssertionError(f"{what}: {int(viol.sum())} elements of |A - L U| beyond the bound, first at row {k[0] + J} column {k[1] + J} "
+                             f"(err {float(err[k]):.3e}, bound {float(bound[k]):.3e})")
+    return float(np.max(np.where(check, err / np.maximum(bound, np.finfo(LD).tiny), 0)))

@@ -72,6 +72,7 @@ int kp_sizeof(const char* name) {
     if (!strcmp(name, "TrsmTask")) return (int)sizeof(sf::TrsmTask);
     if (!strcmp(name, "StepTask")) return (int)sizeof(sf::StepTask);
     if (!strcmp(name, "SolveTask")) return (int)sizeof(sf::SolveTask);
+    if (!strcmp(name, "FillTile")) return (int)sizeof(sf::FillTile);
     return -1;
 }
 
@@ -186,6 +187,49 @@ int kp_step(double* arena, int64_t narena, const sf::StepTask* tasks, int ntasks
     d.out(pivpos, pp, npiv);
     d.out(pivinv, pi, npiv);
     d.out(nperturb, np, 1);
+    return (int)d.rc;
+}
+
+// The LU layout kernels: the L panels at arena + Xp[s], the U^T panels at arena + u_shift + Xp[s].
+// out: nout values, in and out (the launch writes the first e_end - e_begin of them)
+int kp_pack_lu(const double* arena, int64_t narena, int64_t u_shift, const int32_t* Super, const int64_t* Lsip, const int64_t* Xp,
+               const int64_t* RefXp, int32_t nsuper, double* out, int64_t nout, int64_t e_begin, int64_t e_end) {
+    Dev d;
+    const double* A = d.in(arena, narena);
+    const int32_t* S = d.in(Super, (int64_t)nsuper + 1);
+    const int64_t* Lp = d.in(Lsip, (int64_t)nsuper + 1);
+    const int64_t* X = d.in(Xp, nsuper);
+    const int64_t* RX = d.in(RefXp, (int64_t)nsuper + 1);
+    double* O = d.in(out, nout);
+    if (d.rc == hipSuccess) sf::launch_pack_lu(S, Lp, X, RX, nsuper, A, A + u_shift, O, e_begin, e_end, 0);
+    d.finish();
+    d.out(out, O, nout);
+    return (int)d.rc;
+}
+
+int kp_lu_fill_u11(double* arena, int64_t narena, int64_t u_shift, const sf::FillTile* tiles, int64_t ntiles) {
+    Dev d;
+    double* A = d.in(arena, narena);
+    const sf::FillTile* T = d.in(tiles, ntiles);
+    if (d.rc == hipSuccess) sf::launch_lu_fill_u11(T, ntiles, A, A + u_shift, 0);
+    d.finish();
+    d.out(arena, A, narena);
+    return (int)d.rc;
+}
+
+// H: nsuper words, in and out (the launch adds to them)
+int kp_factor_hash(const double* arena, int64_t narena, int64_t u_shift, const int32_t* Super, const int64_t* Lsip, const int64_t* Xp,
+                   const int64_t* RefXp, int32_t nsuper, int lu, int64_t total, unsigned long long* H) {
+    Dev d;
+    const double* A = d.in(arena, narena);
+    const int32_t* S = d.in(Super, (int64_t)nsuper + 1);
+    const int64_t* Lp = d.in(Lsip, (int64_t)nsuper + 1);
+    const int64_t* X = d.in(Xp, nsuper);
+    const int64_t* RX = d.in(RefXp, (int64_t)nsuper + 1);
+    unsigned long long* dH = d.in(H, nsuper);
+    if (d.rc == hipSuccess) sf::launch_factor_hash(S, Lp, X, RX, nsuper, A, A + u_shift, lu, total, dH, 0);
+    d.finish();
+    d.out(H, dH, nsuper);
     return (int)d.rc;
 }
 

@@ -38,6 +38,7 @@ TRSM_TASK = np.dtype([("panel", "<i8"), ("dpanel", "<i8"), ("ld", "<i4"), ("diag
                       ("nrows", "<i4"), ("unit", "<i4"), ("first_col", "<i4"), ("pad", "<i4")])
 SOLVE_TASK = np.dtype([("panel", "<i8"), ("rows", "<i8"), ("ld", "<i4"), ("diag", "<i4"), ("b", "<i4"), ("row0", "<i4"), ("nrows", "<i4"),
                        ("first_col", "<i4"), ("flag", "<i4"), ("expect", "<i4"), ("tdiag", "<i8")])
+FILL_TILE = np.dtype([("xp", "<i8"), ("nsrow", "<i4"), ("r0", "<i4"), ("c0", "<i4"), ("cb", "<i4"), ("ce", "<i4")], align=True)
 
 
 def _make(args, timeout):
@@ -51,7 +52,7 @@ def test_probe_compiles(tmp_path):
     assert r.returncode == 0, r.stdout
     nm = subprocess.run(["nm", "-D", str(tmp_path / "libsf_kprobe.so")], stdout=subprocess.PIPE, text=True).stdout
     for name in ("kp_gemm", "kp_update_small", "kp_potrf", "kp_getrf", "kp_trsm", "kp_step", "kp_build_loadmap", "kp_solve_fwd",
-                 "kp_solve_bwd"):
+                 "kp_solve_bwd", "kp_pack_lu", "kp_lu_fill_u11", "kp_factor_hash"):
         assert f" T {name}" in nm
 
 
@@ -202,7 +203,7 @@ def kp():
     assert r.returncode == 0, r.stdout
     L = C.CDLL(os.path.join(KDIR, "libsf_kprobe.so"))
     for name, dt in (("GemmProb", GEMM_PROB), ("GemmTask", GEMM_TASK), ("PotrfTask", POTRF_TASK), ("TrsmTask", TRSM_TASK), ("StepTask", STEP_TASK),
-                     ("SolveTask", SOLVE_TASK)):
+                     ("SolveTask", SOLVE_TASK), ("FillTile", FILL_TILE)):
         assert L.kp_sizeof(name.encode()) == dt.itemsize, name
     vp, i64, i32, f64 = C.c_void_p, C.c_int64, C.c_int, C.c_double
     L.kp_gemm.argtypes = [vp, i64, vp, i32, vp, i32, vp, C.c_uint32, C.c_uint32, i32, vp, i64, i32, i32, i32]
@@ -214,6 +215,9 @@ def kp():
     L.kp_step.argtypes = [vp, i64, vp, i32, i32, vp, i32, i32, vp, i64, f64, f64, vp, vp, i64, vp]
     L.kp_solve_fwd.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, vp, i64, i32, vp]
     L.kp_solve_bwd.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, i64, i32, vp]
+    L.kp_pack_lu.argtypes = [vp, i64, i64, vp, vp, vp, vp, i32, vp, i64, i64, i64]
+    L.kp_lu_fill_u11.argtypes = [vp, i64, i64, vp, i64]
+    L.kp_factor_hash.argtypes = [vp, i64, i64, vp, vp, vp, vp, i32, i32, i64, vp]
     L.kp_build_loadmap.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, i64, i32, vp]
     L.kp_load_mapped.argtypes = [vp, i64, vp, vp, i64]
     L.kp_load_panels.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp]
