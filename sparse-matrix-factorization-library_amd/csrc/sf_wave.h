@@ -5,6 +5,9 @@
 
 namespace sf {
 
+typedef double double4_t __attribute__((ext_vector_type(4)));
+typedef double double2_t __attribute__((ext_vector_type(2), aligned(8)));   // 16-byte vector that may sit on an 8-byte boundary
+
 // v of lane l (uniform)
 __device__ __forceinline__ double readlane_f64(double v, int l) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);

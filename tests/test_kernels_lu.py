@@ -1,5 +1,6 @@
-"""Single-launch tests of the LU side of csrc/sf_kernels.hip: the fused 64-column step k_step<true> on task lists built here the
-way fused_step() (sf_plan_build.hip) builds them, and the three LU layout kernels (k_pack_lu, k_lu_fill_u11, k_factor_hash).
+"""Single-launch tests of the LU kernels: the fused 64-column step k_step<true> (csrc/sf_step.hip) on task lists built here the
+way fused_step() (sf_plan_build.hip) builds them, and the three LU layout kernels (k_pack_lu, k_lu_fill_u11, k_factor_hash;
+csrc/sf_kernels.hip).
 
 The step tests check the STORED factor of every panel against the panel's matrix element by element (kernel_ref.lu_panel_check:
 |A - L~ U~| <= SAFETY (terms + 2) u |L~| |U~|, rows scaled over 1e-3 .. 1e3), the pivot records against the longdouble rule
@@ -383,7 +384,7 @@ FAILURES = [("zero first column", 0.0), ("zero column", 1.0), ("nan pivot", 0.0)
 @pytest.mark.parametrize("b", [9, 33, 64])
 @pytest.mark.parametrize("kind,tol", FAILURES)
 def test_getrf_reports_zero_and_nan_pivots(kp, kind, tol, b):
-    """k_getrf_block: a zero pivot that is not perturbed, and a NaN pivot, set info bit 0 (sf_kernels.hip, getrf_panel_wave)"""
+    """k_getrf_block: a zero pivot that is not perturbed, and a NaN pivot, set info bit 0 (sf_panel.h, getrf_panel_wave)"""
     inp = _failing_block(np.random.default_rng(b), b, 0, kind)
     ar = LuArena([inp], 0, seed=b)
     off, nscol, nsrow, ld, fc = ar.panels[0]

@@ -1,5 +1,5 @@
 // Where the DIAGONAL workgroup of a fused 64-column step (k_step) spends its time: 100 MHz stamps written by the kernel when it is
-// compiled with -DSF_EXP_STEP_STAMPS (tools/experiments/step_stamps.sh compiles this file together with csrc/sf_kernels.hip).
+// compiled with -DSF_EXP_STEP_STAMPS (tools/experiments/step_stamps.sh compiles this file together with csrc/sf_kernels.hip and csrc/sf_step.hip).
 // One diagonal task + `ntiles` row tiles, step `ti` of its outer block; Cholesky and LU (tol 0.1, natural pivots pass).
 #include <hip/hip_runtime.h>
 #include <cstdio>
