@@ -179,6 +179,17 @@ int sf_chol_plan_refine(sf_chol_plan *plan, const sf_float *b_host, sf_float *x_
 /* w = |A| |x| + |b| (n doubles) of the last residual evaluation of this plan (a residual call, or the last step of a refine
  * call); Cholesky and LU plans; SF_ERR_ARG before the first one */
 int sf_chol_plan_residual_weights(sf_chol_plan *plan, sf_float *w_host);
+/* 1-norm condition estimate with the resident factor: *anorm = |A|_1 of the plan's CURRENT values (the residual's device code),
+ * *ainv_norm_est = a lower bound of |A^{-1}|_1 of the RESIDENT factor that is almost always within a factor 3 of it, so
+ * kappa_1(A) ~ *anorm * *ainv_norm_est when the factor is one of the current values.  The ordering leaves both norms unchanged:
+ * they are the caller's matrix's.  Hager's algorithm as in Higham / LAPACK xLACON: at most 5 passes of one A^{-1} and one A^{-T}
+ * sweep of width 1 (Cholesky: the same sweeps twice), then the alternating-sign safeguard vector -- at most 11 sweeps.  Where
+ * xLACON replaces its estimate by a smaller later column norm, the larger one is kept (both are lower bounds).  The vectors stay
+ * on the device; per pass one 16-byte copy and one synchronisation.  Same plans as sf_chol_plan_refine, and like it refused
+ * (SF_ERR_ARG) when the last factorization that was started has not succeeded; an LU plan is refused here (sf_lu_plan_condest).
+ * Stats: "last_condest_solves" (sweep pairs run), "last_condest_ms" (device time from the first to the last kernel, the waits for
+ * the host's decisions included), "bytes_condest" (2 n + 2 doubles kept after the first call, not in "bytes_device"). */
+int sf_chol_plan_condest(sf_chol_plan *plan, sf_float *anorm, sf_float *ainv_norm_est);
 /* statistics: "levels","launches","gemm_tasks","update_pairs","flops_exec","flops_update",
  * "scatter_elems","bytes_device","last_ms" (device time of the last factorize, HIP events),
  * "last_update_ms","last_panel_ms","last_load_ms" (only when profiling is on) */
@@ -396,6 +407,15 @@ int sf_lu_plan_get_factor(sf_lu_plan *plan, sf_float *Lsx);
 int sf_lu_plan_solve(sf_lu_plan *plan, const sf_float *b_host, sf_float *x_host);
 /* sf_chol_plan_solve_many for an LU plan: X <- (L U)^{-1} B, the plan's pivots applied when pivoting is on */
 int sf_lu_plan_solve_many(sf_lu_plan *plan, sf_long nrhs, const sf_float *B, sf_long ldb, sf_float *X, sf_long ldx);
+/* the transposed solves with the SAME resident factor: x <- A^{-T} b = L^{-T} U^{-T} b, permuted space, the plan's interchanges undone
+ * block by block when pivoting is on (no second analysis or factorization of A^T).  Arguments, chunking, layouts, the in-place
+ * rule and the stats ("last_solve_ms", "last_solve_many_ms") as sf_lu_plan_solve / sf_lu_plan_solve_many.  NULL arguments,
+ * Cholesky plans (A = A^T: use the plain solve), schedule-only, partial, sharded, mapped and out-of-core plans: SF_ERR_ARG; so is a
+ * plan whose last started factorization has not succeeded (as sf_lu_plan_refine). */
+int sf_lu_plan_solve_transposed(sf_lu_plan *plan, const sf_float *b_host, sf_float *x_host);
+int sf_lu_plan_solve_many_transposed(sf_lu_plan *plan, sf_long nrhs, const sf_float *B, sf_long ldb, sf_float *X, sf_long ldx);
+/* sf_chol_plan_condest for an LU plan (pivoting on or off); a Cholesky plan is refused (SF_ERR_ARG) */
+int sf_lu_plan_condest(sf_lu_plan *plan, sf_float *anorm, sf_float *ainv_norm_est);
 /* sf_chol_plan_residual / sf_chol_plan_refine for an LU plan (the solves apply the plan's pivots when pivoting is on); a Cholesky
  * plan is refused (SF_ERR_ARG) */
 int sf_lu_plan_residual(sf_lu_plan *plan, const sf_float *b_host, const sf_float *x_host,

@@ -239,6 +239,13 @@ lib.sf_lu_plan_solve.argtypes = [C.c_void_p, c_double_p, c_double_p]
 lib.sf_lu_plan_solve.restype = C.c_int
 lib.sf_lu_plan_solve_many.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64]
 lib.sf_lu_plan_solve_many.restype = C.c_int
+lib.sf_lu_plan_solve_transposed.argtypes = [C.c_void_p, c_double_p, c_double_p]
+lib.sf_lu_plan_solve_transposed.restype = C.c_int
+lib.sf_lu_plan_solve_many_transposed.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64]
+lib.sf_lu_plan_solve_many_transposed.restype = C.c_int
+for _n in ("sf_chol_plan_condest", "sf_lu_plan_condest"):
+    getattr(lib, _n).argtypes = [C.c_void_p, c_double_p, c_double_p]
+    getattr(lib, _n).restype = C.c_int
 lib.sf_lu_plan_selinv.argtypes = [C.c_void_p]
 lib.sf_lu_plan_selinv.restype = C.c_int
 lib.sf_lu_plan_get_selinv_range.argtypes = [C.c_void_p, C.c_int64, C.c_int64, c_double_p]

@@ -442,7 +442,17 @@ class _RefineMixin:
         return x, {"iters": int(self.stat("last_refine_iters")), "berr0": self.stat("last_refine_berr0"), "berr": berr.value}
 
 
-class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin):
+class _CondestMixin:
+    def condest(self, return_parts=False):
+        """1-norm condition estimate kappa_1(A) ~ |A|_1 * est(|A^-1|_1) (Hager / Higham, at most 11 device sweeps with the
+        resident factor; the estimate of |A^-1|_1 is a lower bound).  return_parts: (|A|_1, estimate of |A^-1|_1)"""
+        fn = lib.sf_lu_plan_condest if isinstance(self, LUPlan) else lib.sf_chol_plan_condest
+        anorm, ainv = C.c_double(), C.c_double()
+        check(fn(self._h, C.byref(anorm), C.byref(ainv)), fn.__name__)
+        return (anorm.value, ainv.value) if return_parts else anorm.value * ainv.value
+
+
+class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin):
     """Device-resident supernodal Cholesky (flat ABI).  Raises if no HIP device is present.
     phase/load_top: multi-GPU sharding (sf_chol_plan_create_sharded); default = the whole matrix on one device.
     rank/nranks (with phase): distributed top (sf_chol_plan_create_distributed), run with factorize_phase(0) and then
@@ -558,7 +568,7 @@ class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin):
         self.close()
 
 
-class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin):
+class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin):
     """Device-resident supernodal no-pivot LU (flat ABI, sf_lu_plan_*).  `sym` comes from analyze(..., method='lu').
     phase/load_top/rank/nranks: distributed multi-GPU plan (sf_lu_plan_create_distributed), as CholPlan."""
 
@@ -634,16 +644,23 @@ class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin):
         check(lib.sf_chol_plan_factorize_to_host(self._h, _dp(Lx), ux, _dp(out)), "sf_chol_plan_factorize_to_host")
         return out[:self.xsize]
 
-    def solve(self, b):
+    def solve(self, b, trans=False):
+        """x = A^-1 b, or A^-T b with trans=True (the same resident factor); a 2-D b goes to solve_many"""
         if np.ndim(b) == 2:
-            return self.solve_many(b)
+            return self.solve_many(b, trans)
         b = _f64(b)
         x = np.empty_like(b)
-        check(lib.sf_lu_plan_solve(self._h, _dp(b), _dp(x)), "sf_lu_plan_solve")
+        if trans:
+            check(lib.sf_lu_plan_solve_transposed(self._h, _dp(b), _dp(x)), "sf_lu_plan_solve_transposed")
+        else:
+            check(lib.sf_lu_plan_solve(self._h, _dp(b), _dp(x)), "sf_lu_plan_solve")
         return x
 
-    def solve_many(self, B):
-        """X = A^-1 B for an (n, k) block of right-hand sides (any memory order), permuted space, 16 columns per device sweep"""
+    def solve_many(self, B, trans=False):
+        """X = A^-1 B (trans=True: A^-T B) for an (n, k) block of right-hand sides (any memory order), permuted space, 16 columns
+        per device sweep"""
+        if trans:
+            return _solve_many(lib.sf_lu_plan_solve_many_transposed, "sf_lu_plan_solve_many_transposed", self._h, self.n, B)
         return _solve_many(lib.sf_lu_plan_solve_many, "sf_lu_plan_solve_many", self._h, self.n, B)
 
     def selinv(self):

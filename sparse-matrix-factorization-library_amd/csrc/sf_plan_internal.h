@@ -135,6 +135,13 @@ void sf_solve_sweep_bwd(sf_chol_plan* p, double* x, int width, bool transpose_di
 void sf_solve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, hipStream_t st);
 // the end of a solve: read the info word, synchronize; SF_ERR_HIP if a bounded in-launch wait ran out
 int sf_solve_finish(sf_chol_plan* p, hipStream_t st);
+// ---- shared with the condition estimate and the transposed solves (sf_refine.hip) ----
+// the last factorization that was started has succeeded (a finished but unsynchronised one is collected here); an imported factor
+// counts.  NOT required: that it is a factorization of the current values.
+bool sf_factor_usable(sf_chol_plan* p);
+// *d_anorm = device address of |A|_1 of the plan's CURRENT values, up to date on `st` (the residual's row / column form is set up by
+// the first call, the norm recomputed when factor_gen has moved); the plans sf_chol_plan_residual accepts
+int sf_refine_anorm(sf_chol_plan* p, const double** d_anorm, hipStream_t st);
 
 struct sf_chol_plan {
     // ---- overlapped download schedule (built once) and the state of a running download ----
@@ -289,6 +296,12 @@ struct sf_chol_plan {
     size_t bytes_refine = 0;
     int last_refine_iters = 0;
     double last_refine_berr0 = 0, last_refine_berr = 0, last_refine_ms = 0, last_residual_ms = 0;
+    // sf_*_plan_condest (sf_solve_t.hip): x | the sign vector | the iteration's scalars, allocated by the first call (not in
+    // bytes_device)
+    double* d_cond = nullptr;
+    size_t bytes_condest = 0;
+    int last_condest_solves = 0;
+    double last_condest_ms = 0;
     int device = 0;
     int64_t n = 0, nsuper = 0, nnz = 0, isize = 0, xsize = 0;
     hipStream_t stream = nullptr;

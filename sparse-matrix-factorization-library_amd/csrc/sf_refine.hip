@@ -147,13 +147,6 @@ bool refine_refused(const sf_chol_plan* p) {
     return p->dry || p->partial || p->nranks > 1 || p->ooc_groups > 1 || !p->d_loadmapL || (p->lu && !p->d_loadmapU);
 }
 
-// the last factorization that was started has succeeded (a finished but unsynchronised one is collected here); an imported
-// factor counts.  NOT required: that it is a factorization of the current values.
-bool factor_usable(sf_chol_plan* p) {
-    if (p->fact_done && p->ok_gen < p->fact_gen) (void)sf_chol_plan_sync(p);
-    return p->ok_gen >= 0 && p->ok_gen >= p->fact_gen;
-}
-
 template <class T>
 int fetch(std::vector<T>& h, const T* d, int64_t count) {
     h.resize((size_t)std::max<int64_t>(count, 0));
@@ -269,16 +262,22 @@ sf::RefineForm row_form(const sf_chol_plan* p) {
     return sf::RefineForm{p->d_rf_ptr, p->d_rf_col, p->d_rf_pos, unsym ? p->d_Ux : p->d_Lx, p->d_Lx};
 }
 
+// v.s[5] = |A|_1 of the current values: the column sums of |A| (unsymmetric LU: the column form; symmetric: the row form serves),
+// recomputed when the values have changed
+int refine_anorm(sf_chol_plan* p, const RefineVecs& v, hipStream_t st) {
+    if (p->rf_anorm_gen == p->factor_gen) return SF_OK;
+    const bool unsym = p->lu && !p->u_alias;
+    HIP_TRY(hipMemsetAsync(v.s + 5, 0, sizeof(double), st));
+    sf::launch_refine_abs_sums(unsym ? sf::RefineForm{p->d_rf_cptr, p->d_rf_ccol, p->d_rf_cpos, p->d_Lx, p->d_Ux} : row_form(p), p->n,
+                               v.s + 5, st);
+    p->rf_anorm_gen = p->factor_gen;
+    return SF_OK;
+}
+
 // r = b - A x, w, and the scalars on the device (nothing waits here).  |A|_1 is recomputed when the values have changed.
 int refine_eval(sf_chol_plan* p, const RefineVecs& v, const double* x, bool after_solve, hipStream_t st) {
     HIP_TRY(hipMemsetAsync(v.s, 0, 5 * sizeof(double), st));
-    if (p->rf_anorm_gen != p->factor_gen) {
-        const bool unsym = p->lu && !p->u_alias;
-        HIP_TRY(hipMemsetAsync(v.s + 5, 0, sizeof(double), st));
-        sf::launch_refine_abs_sums(unsym ? sf::RefineForm{p->d_rf_cptr, p->d_rf_ccol, p->d_rf_cpos, p->d_Lx, p->d_Ux} : row_form(p), p->n,
-                                   v.s + 5, st);
-        p->rf_anorm_gen = p->factor_gen;
-    }
+    if (int rc = refine_anorm(p, v, st)) return rc;
     sf::launch_refine_resid(row_form(p), p->n, x, v.b, v.r, v.w, st);
     sf::launch_refine_norms(p->n, v.r, v.w, x, v.b, after_solve ? p->d_solve_sync : nullptr, v.s, st);
     HIP_TRY(hipGetLastError());
@@ -308,6 +307,21 @@ int refine_read(sf_chol_plan* p, const RefineVecs& v, RefineScalars* out, hipStr
 
 }  // namespace
 
+bool sf_factor_usable(sf_chol_plan* p) {
+    if (p->fact_done && p->ok_gen < p->fact_gen) (void)sf_chol_plan_sync(p);
+    return p->ok_gen >= 0 && p->ok_gen >= p->fact_gen;
+}
+
+int sf_refine_anorm(sf_chol_plan* p, const double** d_anorm, hipStream_t st) {
+    if (refine_refused(p) || !p->values_set) return SF_ERR_ARG;
+    if (int rc = refine_setup(p)) return rc;
+    const RefineVecs v = refine_vecs(p);
+    if (int rc = refine_anorm(p, v, st)) return rc;
+    HIP_TRY(hipGetLastError());
+    *d_anorm = v.s + 5;
+    return SF_OK;
+}
+
 extern "C" {
 
 int sf_chol_plan_residual(sf_chol_plan* p, const sf_float* b_host, const sf_float* x_host, sf_float* r_host, sf_float* berr, sf_float* nerr) {
@@ -323,13 +337,7 @@ int sf_chol_plan_residual(sf_chol_plan* p, const sf_float* b_host, const sf_floa
     const size_t nb = (size_t)p->n * sizeof(double);
     HIP_TRY(hipMemcpyAsync(v.b, b_host, nb, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(v.x, x_host, nb, hipMemcpyHostToDevice, st));
-    if (p->rf_anorm_gen != p->factor_gen) {     // (so that the timed stretch below holds the residual pass alone)
-        HIP_TRY(hipMemsetAsync(v.s + 5, 0, sizeof(double), st));
-        const bool unsym = p->lu && !p->u_alias;
-        sf::launch_refine_abs_sums(unsym ? sf::RefineForm{p->d_rf_cptr, p->d_rf_ccol, p->d_rf_cpos, p->d_Lx, p->d_Ux} : row_form(p), p->n,
-                                   v.s + 5, st);
-        p->rf_anorm_gen = p->factor_gen;
-    }
+    if (int rc = refine_anorm(p, v, st)) return rc;     // (here, so that the timed stretch below holds the residual pass alone)
     HIP_TRY(hipMemsetAsync(v.s, 0, 5 * sizeof(double), st));
     HIP_TRY(hipEventRecord(p->ev_s0, st));
     sf::launch_refine_resid(row_form(p), p->n, v.x, v.b, v.r, v.w, st);
@@ -359,7 +367,7 @@ int sf_chol_plan_refine(sf_chol_plan* p, const sf_float* b_host, sf_float* x_hos
     if (!p || !b_host || !x_host || max_iter < 0) return SF_ERR_ARG;
     if (refine_refused(p) || !p->values_set || (p->nsuper > 0 && !p->d_solve)) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
-    if (!factor_usable(p)) return SF_ERR_ARG;
+    if (!sf_factor_usable(p)) return SF_ERR_ARG;
     if (berr_out) *berr_out = 0.0;
     p->last_refine_iters = 0;
     p->last_refine_berr0 = p->last_refine_berr = 0.0;
