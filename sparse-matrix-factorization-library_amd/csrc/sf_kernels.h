@@ -197,6 +197,23 @@ void launch_solve_bwd(const SolveTask* t, int nt, int width, int big, const doub
 // row-major copies of the diagonal blocks of the backward diagonal tasks list[0 .. ntasks) (indices into `tasks`) into T
 void launch_solve_transpose_diag(const SolveTask* tasks, const int64_t* list, int64_t ntasks, const double* Lsx, double* T, hipStream_t st);
 
+// the transposed backward sweep over the L panels of an LU plan (sf_solve_t.hip): launch_solve_small_bwd's / launch_solve_bwd's task
+// lists, sync words and tickets; the diagonal is implied, and with pivpos != nullptr a block's interchanges are undone after its chain
+void launch_tsolve_small_bwd(const SolveTask* t, int nt, int width, const double* Lsx, const int32_t* Lsi, double* x, const int32_t* pivpos,
+                             hipStream_t st);
+void launch_tsolve_bwd(const SolveTask* t, int nt, int width, int big, const double* Lsx, const int32_t* Lsi, double* x,
+                       const int32_t* pivpos, int* sync, int* ticket, int* info, hipStream_t st, const double* Tbase);
+
+// ---- the 1-norm condition estimate's device steps (sf_solve_t.hip, sf_*_plan_condest) ----
+struct CondScalars { double nrm; int32_t flags, j; };      // flags: bit 0 = sign vector unchanged, bit 1 = x was the safeguard vector,
+                                                            // bit 2 = the info word of the sweeps before (a bounded wait ran out)
+// mode 0: x = 1 / n;  mode 2: the safeguard vector x_i = (-1)^i (1 + i / (n - 1)), n > 1
+void launch_condest_fill(double* x, int64_t n, int mode, hipStream_t st);
+// s->nrm = |y|_1, bit 0 of s->flags = (sign(y) == xi everywhere), bit 2 = (*solve_info != 0), bit 1 kept; then xi = y = sign(y)
+void launch_condest_sign_norm(double* y, double* xi, int64_t n, const int* solve_info, CondScalars* s, hipStream_t st);
+// s->j = the first index of the largest |x_i|; x = e_j, or (stopping: s->flags = 2) the safeguard vector; n > 1
+void launch_condest_argmax_next(double* x, int64_t n, CondScalars* s, int first, int last, hipStream_t st);
+
 // column-major n x cw (leading dimension n) -> row-major n x SVM_W, columns [cw, SVM_W) zero; and back (columns [0, cw) only)
 void launch_solve_many_pack(const double* Bc, int64_t n, int cw, double* X, hipStream_t st);
 void launch_solve_many_unpack(const double* X, int64_t n, int cw, double* Bc, hipStream_t st);

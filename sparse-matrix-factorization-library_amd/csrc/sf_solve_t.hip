@@ -319,14 +319,14 @@ static bool tsv_single(int width) {
     assert(width == 1 || width == SVM_W);       // x has one of two layouts: any other width would run a kernel on the wrong one
     return width == 1;
 }
-static void launch_tsolve_small_bwd(const SolveTask* t, int nt, int width, const double* Lsx, const int32_t* Lsi, double* x, const int32_t* pivpos,
-                                    hipStream_t st) {
+void launch_tsolve_small_bwd(const SolveTask* t, int nt, int width, const double* Lsx, const int32_t* Lsi, double* x, const int32_t* pivpos,
+                             hipStream_t st) {
     if (nt <= 0) return;
     hipLaunchKernelGGL(tsv_single(width) ? k_tsolve_small_bwd : k_tsolve_many_small_bwd, dim3((nt + 3) / 4), dim3(256), 0, st, t, nt, Lsx, Lsi, x,
                        pivpos);
 }
-static void launch_tsolve_bwd(const SolveTask* t, int nt, int width, int big, const double* Lsx, const int32_t* Lsi, double* x,
-                              const int32_t* pivpos, int* sync, int* ticket, int* info, hipStream_t st, const double* Tbase) {
+void launch_tsolve_bwd(const SolveTask* t, int nt, int width, int big, const double* Lsx, const int32_t* Lsi, double* x,
+                       const int32_t* pivpos, int* sync, int* ticket, int* info, hipStream_t st, const double* Tbase) {
     if (nt <= 0) return;
     const auto k = tsv_single(width) ? (big ? k_tsolve_bwd<true> : k_tsolve_bwd<false>) : (big ? k_tsolve_many_bwd<true> : k_tsolve_many_bwd<false>);
     hipLaunchKernelGGL(k, dim3(nt), dim3(256), 0, st, t, Lsx, Lsi, x, pivpos, sync, ticket, info, Tbase);
@@ -338,8 +338,6 @@ static void launch_tsolve_bwd(const SolveTask* t, int nt, int width, int big, co
 // fixed order (no floating-point atomics: the same factor gives the same estimate on every call).
 // ---------------------------------------------------------------------------------------------------
 constexpr int CE_T = 1024;
-struct CondScalars { double nrm; int32_t flags, j; };      // flags: bit 0 = sign vector unchanged, bit 1 = x was the safeguard vector,
-                                                            // bit 2 = the info word of the sweeps before (a bounded wait ran out)
 static_assert(sizeof(CondScalars) == 16, "the one small copy of an iteration");
 
 // the safeguard vector x_i = (-1)^i (1 + i / (n - 1)), n > 1
@@ -424,6 +422,17 @@ k_condest_argmax_next(double* __restrict__ x, int64_t n, CondScalars* __restrict
     for (int64_t i = tid; i < n; i += CE_T) x[i] = stop ? ce_altsgn(i, n) : (i == j ? 1.0 : 0.0);
 }
 
+void launch_condest_fill(double* x, int64_t n, int mode, hipStream_t st) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_condest_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, n, mode);
+}
+void launch_condest_sign_norm(double* y, double* xi, int64_t n, const int* solve_info, CondScalars* s, hipStream_t st) {
+    hipLaunchKernelGGL(k_condest_sign_norm, dim3(1), dim3(CE_T), 0, st, y, xi, n, solve_info, s);
+}
+void launch_condest_argmax_next(double* x, int64_t n, CondScalars* s, int first, int last, hipStream_t st) {
+    hipLaunchKernelGGL(k_condest_argmax_next, dim3(1), dim3(CE_T), 0, st, x, n, s, first, last);
+}
+
 }  // namespace sf
 
 // ---------------------------------------------------------------------------------------------------
@@ -492,7 +501,6 @@ int condest(sf_chol_plan* p, sf_float* anorm, sf_float* ainv_norm_est) {
     double* xi = x + n;
     sf::CondScalars* ds = (sf::CondScalars*)(xi + n);
     const size_t sync_bytes = sf_solve_sync(p).bytes;
-    const unsigned fill_grid = (unsigned)((n + 255) / 256);
     int solves = 0;
     bool solve_failed = false;
     // A^{-1} x and A^{-T} x in place.  LU: each sweep pair makes its own row-major diagonal copies (see tsolve_sweeps); Cholesky: the
@@ -516,9 +524,9 @@ int condest(sf_chol_plan* p, sf_float* anorm, sf_float* ainv_norm_est) {
     hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
     HIP_TRY(hipEventRecord(e0, st));
     HIP_TRY(hipMemsetAsync(xi, 0, ((size_t)n + 2) * sizeof(double), st));
-    hipLaunchKernelGGL(sf::k_condest_fill, dim3(fill_grid), dim3(256), 0, st, x, n, 0);
+    sf::launch_condest_fill(x, n, 0, st);
     if (int rc = sweep(false)) return rc;
-    hipLaunchKernelGGL(sf::k_condest_sign_norm, dim3(1), dim3(sf::CE_T), 0, st, x, xi, n, (const int*)p->d_solve_sync, ds);
+    sf::launch_condest_sign_norm(x, xi, n, (const int*)p->d_solve_sync, ds, st);
     double h_anorm = 0.0;
     HIP_TRY(hipMemcpyAsync(&h_anorm, d_anorm, sizeof(double), hipMemcpyDeviceToHost, st));
     if (int rc = read()) return rc;
@@ -529,9 +537,9 @@ int condest(sf_chol_plan* p, sf_float* anorm, sf_float* ainv_norm_est) {
     // k_condest_argmax_next decides it on the device and says which it was.  At most 1 + 5 + 4 + 1 = 11 sweeps.
     for (int iter = 1; n > 1 && std::isfinite(est) && !solve_failed; ++iter) {
         if (int rc = sweep(true)) return rc;                                            // x = A^{-T} xi
-        hipLaunchKernelGGL(sf::k_condest_argmax_next, dim3(1), dim3(sf::CE_T), 0, st, x, n, ds, iter == 1 ? 1 : 0, iter >= ITMAX ? 1 : 0);
+        sf::launch_condest_argmax_next(x, n, ds, iter == 1 ? 1 : 0, iter >= ITMAX ? 1 : 0, st);
         if (int rc = sweep(false)) return rc;                                           // x = A^{-1} (e_j or the safeguard vector)
-        hipLaunchKernelGGL(sf::k_condest_sign_norm, dim3(1), dim3(sf::CE_T), 0, st, x, xi, n, (const int*)p->d_solve_sync, ds);
+        sf::launch_condest_sign_norm(x, xi, n, (const int*)p->d_solve_sync, ds, st);
         if (int rc = read()) return rc;
         const bool safeguard = (h.flags & 2) != 0;
         if (!safeguard) {
@@ -540,9 +548,9 @@ int condest(sf_chol_plan* p, sf_float* anorm, sf_float* ainv_norm_est) {
             est = std::isfinite(h.nrm) ? std::max(est, h.nrm) : h.nrm;
             if (go_on) continue;
             if (!std::isfinite(est) || solve_failed) break;
-            hipLaunchKernelGGL(sf::k_condest_fill, dim3(fill_grid), dim3(256), 0, st, x, n, 2);
+            sf::launch_condest_fill(x, n, 2, st);
             if (int rc = sweep(false)) return rc;
-            hipLaunchKernelGGL(sf::k_condest_sign_norm, dim3(1), dim3(sf::CE_T), 0, st, x, xi, n, (const int*)p->d_solve_sync, ds);
+            sf::launch_condest_sign_norm(x, xi, n, (const int*)p->d_solve_sync, ds, st);
             if (int rc = read()) return rc;
         }
         const double alt = 2.0 * h.nrm / (3.0 * (double)n);

@@ -172,7 +172,7 @@ def getrf_rule(A, tol, eps):
 def assert_equations(total, rhs, nterms, mag, cols, what):
     """one equation per element: `total` (longdouble: the sum of the equation's products, formed from the stored results)
     against its right-hand side, |total - rhs| <= SAFETY nterms u mag with nterms = the number of terms of the sum and mag = the
-    sum of their magnitudes (|rhs| among them where rhs is itself a summand).  Only the columns `cols` are checked (the others may hold a planted NaN)."""
+    sum of their magnitudes (|rhs| among them where rhs is itself a summand).  Only the columns `cols` are checked (the others may hold a planted NaN).  Returns the worst err / bound over them."""
     total, mag = np.asarray(total, dtype=LD)[:, cols], np.asarray(mag, dtype=LD)[:, cols]
     rhs = np.asarray(rhs, dtype=LD)[:, cols]
     if not np.all(np.isfinite(total)):
@@ -180,10 +180,57 @@ def assert_equations(total, rhs, nterms, mag, cols, what):
     err = np.abs(total - rhs)
     bound = SAFETY * np.asarray(nterms, dtype=LD).reshape(-1, 1) * U * mag
     viol = err > bound
+    worst = float(np.max(err / np.maximum(bound, np.finfo(LD).tiny), initial=0.0))
     if viol.any():
         k = tuple(np.argwhere(viol)[0])
         raise AssertionError(f"{what}: {int(viol.sum())} of {viol.size} equations beyond the bound, first at {list(k)} "
-                             f"(err {float(err[k]):.3e}, bound {float(bound[k]):.3e})")
+                             f"(err {float(err[k]):.3e}, bound {float(bound[k]):.3e}, worst err / bound {worst:.3g})")
+    return worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the transposed backward launch of the device solve (csrc/sf_solve_t.hip): tests/test_kernels_tsolve.py
+# ---------------------------------------------------------------------------------------------------------------------
+def tsolve_matrix(D, pos, nb=64):
+    """M of one panel's block as the forward launch with unit = 1 and the same interchanges sees it (the statement the transposed
+    launch is the adjoint of): S = the strictly lower part of D with a unit diagonal; inside each nb-row sub-block, row l of the
+    diagonal sub-block is S[pos[l]]; left of the sub-block the rows are their own."""
+    b = D.shape[0]
+    S = np.tril(D, -1) + np.eye(b)
+    M = S.copy()
+    for s in range(0, b, nb):
+        M[s:s + nb, s:s + nb] = S[pos[s:s + nb], s:s + nb]
+    return M
+
+
+TSOLVE_FAULTS = ("forward permutation", "late interchange", "stored diagonal")
+
+
+def tsolve_emulate(D, Lb, pos, xblk, xrows, fault=None, nb=64):
+    """plain float64 emulation of the transposed backward launch on one panel: the tiles subtract Lb^T x[rows]; then the sub-blocks
+    from the last to the first: the unit upper chain (L^T of the sub-block, from its last row up), the inverse interchange
+    z[l] = w[pos[l]], then the subtraction from the earlier sub-blocks.  fault: one of TSOLVE_FAULTS, a single corruption --
+    z[pos[l]] = w[l]; the earlier sub-blocks read before the interchange; D's own diagonal in place of the implied 1."""
+    assert fault is None or fault in TSOLVE_FAULTS
+    b = D.shape[0]
+    v = np.array(xblk, dtype=np.float64)
+    v -= Lb.T @ xrows
+    for s in reversed(range(0, b, nb)):
+        e = min(s + nb, b)
+        w = v[s:e].copy()
+        for j in reversed(range(s, e)):
+            if fault == "stored diagonal":
+                w[j - s] = w[j - s] / D[j, j]
+            w[:j - s] -= D[j, s:j, None] * w[j - s]
+        local = pos[s:e] - s
+        z = np.empty_like(w)
+        if fault == "forward permutation":
+            z[local] = w
+        else:
+            z = w[local]
+        v[s:e] = z
+        v[:s] -= D[s:e, :s].T @ (w if fault == "late interchange" else z)
+    return v
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -73,6 +73,7 @@ int kp_sizeof(const char* name) {
     if (!strcmp(name, "StepTask")) return (int)sizeof(sf::StepTask);
     if (!strcmp(name, "SolveTask")) return (int)sizeof(sf::SolveTask);
     if (!strcmp(name, "FillTile")) return (int)sizeof(sf::FillTile);
+    if (!strcmp(name, "CondScalars")) return (int)sizeof(sf::CondScalars);
     return -1;
 }
 
@@ -282,6 +283,92 @@ int kp_solve_bwd(double* arena, int64_t narena, const int32_t* Lsi, int64_t nLsi
     d.out(arena, A, narena);
     d.out(x, X, nx * width);
     d.out(info, W, 1);
+    return (int)d.rc;
+}
+
+// The transposed backward launch over the same task lists (csrc/sf_solve_t.hip): arena = the L panels (diagonal implied), pivpos:
+// npiv entries or null.  nT > 0: the row-major copies are made from the same arena first, as the transposed sweep does.
+int kp_tsolve_bwd(double* arena, int64_t narena, const int32_t* Lsi, int64_t nLsi, double* x, int64_t nx, const sf::SolveTask* tasks,
+                  int ntasks, int width, int big, int small, const int32_t* pivpos, int64_t npiv, int64_t nT, int nsync, int* info) {
+    Dev d;
+    double* A = d.in(arena, narena);
+    const int32_t* L = d.in(Lsi, nLsi);
+    double* X = d.in(x, nx * width);
+    const sf::SolveTask* T = d.in(tasks, ntasks);
+    const int32_t* pp = pivpos ? d.in(pivpos, npiv) : nullptr;
+    int* W = d.in<int>(nullptr, 2 + (int64_t)nsync);
+    double* Tb = nT > 0 ? d.in<double>(nullptr, nT) : nullptr;
+    std::vector<int64_t> list;
+    for (int i = 0; Tb && i < ntasks; ++i)
+        if (tasks[i].nrows == 0 && tasks[i].tdiag) list.push_back(i);
+    const int64_t* dl = d.in(list.data(), (int64_t)list.size());
+    if (d.rc == hipSuccess) {
+        int *sync = W + 1, *ticket = W + 1 + nsync;
+        sf::launch_solve_transpose_diag(T, dl, (int64_t)list.size(), A, Tb, 0);
+        if (small) sf::launch_tsolve_small_bwd(T, ntasks, width, A, L, X, pp, 0);
+        else sf::launch_tsolve_bwd(T, ntasks, width, big, A, L, X, pp, sync, ticket, W, 0, Tb);
+    }
+    d.finish();
+    d.out(arena, A, narena);
+    d.out(x, X, nx * width);
+    d.out(info, W, 1);
+    return (int)d.rc;
+}
+
+// The condition estimate's kernels.  x / y / xi: `len` doubles each, in and out (len >= n: the tail is the test's sentinel);
+// scalars: the 16-byte CondScalars, in and out
+int kp_condest_fill(double* x, int64_t len, int64_t n, int mode) {
+    Dev d;
+    double* X = d.in(x, len);
+    if (d.rc == hipSuccess) sf::launch_condest_fill(X, n, mode, 0);
+    d.finish();
+    d.out(x, X, len);
+    return (int)d.rc;
+}
+
+int kp_condest_sign_norm(double* y, double* xi, int64_t len, int64_t n, int solve_info_value, sf::CondScalars* scalars) {
+    Dev d;
+    double* Y = d.in(y, len);
+    double* Xi = d.in(xi, len);
+    const int* I = d.in(&solve_info_value, 1);
+    sf::CondScalars* S = d.in(scalars, 1);
+    if (d.rc == hipSuccess) sf::launch_condest_sign_norm(Y, Xi, n, I, S, 0);
+    d.finish();
+    d.out(y, Y, len);
+    d.out(xi, Xi, len);
+    d.out(scalars, S, 1);
+    return (int)d.rc;
+}
+
+int kp_condest_argmax_next(double* x, int64_t len, int64_t n, sf::CondScalars* scalars, int first, int last) {
+    Dev d;
+    double* X = d.in(x, len);
+    sf::CondScalars* S = d.in(scalars, 1);
+    if (d.rc == hipSuccess) sf::launch_condest_argmax_next(X, n, S, first, last, 0);
+    d.finish();
+    d.out(x, X, len);
+    d.out(scalars, S, 1);
+    return (int)d.rc;
+}
+
+// Bc: nBc doubles (column-major n x cw in front), X: nX doubles (row-major n x SVM_W in front); the destination in and out
+int kp_solve_many_pack(const double* Bc, int64_t nBc, int64_t n, int cw, double* X, int64_t nX) {
+    Dev d;
+    const double* B = d.in(Bc, nBc);
+    double* Xd = d.in(X, nX);
+    if (d.rc == hipSuccess) sf::launch_solve_many_pack(B, n, cw, Xd, 0);
+    d.finish();
+    d.out(X, Xd, nX);
+    return (int)d.rc;
+}
+
+int kp_solve_many_unpack(const double* X, int64_t nX, int64_t n, int cw, double* Bc, int64_t nBc) {
+    Dev d;
+    const double* Xd = d.in(X, nX);
+    double* B = d.in(Bc, nBc);
+    if (d.rc == hipSuccess) sf::launch_solve_many_unpack(Xd, n, cw, B, 0);
+    d.finish();
+    d.out(Bc, B, nBc);
     return (int)d.rc;
 }
 

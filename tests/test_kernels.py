@@ -39,6 +39,7 @@ TRSM_TASK = np.dtype([("panel", "<i8"), ("dpanel", "<i8"), ("ld", "<i4"), ("diag
 SOLVE_TASK = np.dtype([("panel", "<i8"), ("rows", "<i8"), ("ld", "<i4"), ("diag", "<i4"), ("b", "<i4"), ("row0", "<i4"), ("nrows", "<i4"),
                        ("first_col", "<i4"), ("flag", "<i4"), ("expect", "<i4"), ("tdiag", "<i8")])
 FILL_TILE = np.dtype([("xp", "<i8"), ("nsrow", "<i4"), ("r0", "<i4"), ("c0", "<i4"), ("cb", "<i4"), ("ce", "<i4")], align=True)
+COND_SCALARS = np.dtype([("nrm", "<f8"), ("flags", "<i4"), ("j", "<i4")])
 
 
 def _make(args, timeout):
@@ -52,7 +53,8 @@ def test_probe_compiles(tmp_path):
     assert r.returncode == 0, r.stdout
     nm = subprocess.run(["nm", "-D", str(tmp_path / "libsf_kprobe.so")], stdout=subprocess.PIPE, text=True).stdout
     for name in ("kp_gemm", "kp_update_small", "kp_potrf", "kp_getrf", "kp_trsm", "kp_step", "kp_build_loadmap", "kp_solve_fwd",
-                 "kp_solve_bwd", "kp_pack_lu", "kp_lu_fill_u11", "kp_factor_hash"):
+                 "kp_solve_bwd", "kp_pack_lu", "kp_lu_fill_u11", "kp_factor_hash", "kp_tsolve_bwd", "kp_condest_fill", "kp_condest_sign_norm",
+                 "kp_condest_argmax_next", "kp_solve_many_pack", "kp_solve_many_unpack"):
         assert f" T {name}" in nm
 
 
@@ -232,7 +234,7 @@ def kp():
     assert r.returncode == 0, r.stdout
     L = C.CDLL(os.path.join(KDIR, "libsf_kprobe.so"))
     for name, dt in (("GemmProb", GEMM_PROB), ("GemmTask", GEMM_TASK), ("PotrfTask", POTRF_TASK), ("TrsmTask", TRSM_TASK), ("StepTask", STEP_TASK),
-                     ("SolveTask", SOLVE_TASK), ("FillTile", FILL_TILE)):
+                     ("SolveTask", SOLVE_TASK), ("FillTile", FILL_TILE), ("CondScalars", COND_SCALARS)):
         assert L.kp_sizeof(name.encode()) == dt.itemsize, name
     vp, i64, i32, f64 = C.c_void_p, C.c_int64, C.c_int, C.c_double
     L.kp_gemm.argtypes = [vp, i64, vp, i32, vp, i32, vp, C.c_uint32, C.c_uint32, i32, vp, i64, i32, i32, i32]
@@ -244,6 +246,12 @@ def kp():
     L.kp_step.argtypes = [vp, i64, vp, i32, i32, vp, i32, i32, vp, i64, f64, f64, vp, vp, i64, vp]
     L.kp_solve_fwd.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, vp, i64, i32, vp]
     L.kp_solve_bwd.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, i64, i32, vp]
+    L.kp_tsolve_bwd.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, vp, i64, i64, i32, vp]
+    L.kp_condest_fill.argtypes = [vp, i64, i64, i32]
+    L.kp_condest_sign_norm.argtypes = [vp, vp, i64, i64, i32, vp]
+    L.kp_condest_argmax_next.argtypes = [vp, i64, i64, vp, i32, i32]
+    L.kp_solve_many_pack.argtypes = [vp, i64, i64, i32, vp, i64]
+    L.kp_solve_many_unpack.argtypes = [vp, i64, i64, i32, vp, i64]
     L.kp_pack_lu.argtypes = [vp, i64, i64, vp, vp, vp, vp, i32, vp, i64, i64, i64]
     L.kp_lu_fill_u11.argtypes = [vp, i64, i64, vp, i64]
     L.kp_factor_hash.argtypes = [vp, i64, i64, vp, vp, vp, vp, i32, i32, i64, vp]
@@ -1089,6 +1097,36 @@ def _solve_check_bwd(case, x1, what):
                             f"{what} b={b} below={p['below']}")
         written[p["blk"]] = True
     kr.assert_unchanged(x0, x1, written, what)
+
+
+def _tsolve_run(kp, case, a, tasks, width, big, small, pivpos=None, nT=0):
+    """one transposed backward launch (csrc/sf_solve_t.hip) on the L panels of `a`; pivpos: the interchange record, or None"""
+    x, before, info = case.x.copy(), a.copy(), np.full(1, -1, dtype=np.int32)
+    nsync = 2 * len(case.panels) + 1
+    _ok(kp.kp_tsolve_bwd(P(a), len(a), P(case.lsi), len(case.lsi), P(x), case.nx, P(tasks), len(tasks), width, big, small, P(pivpos), case.nx,
+                         nT, nsync, P(info)))
+    assert info[0] == 0, info
+    assert np.array_equal(kr.bits(before), kr.bits(a)), "the factor arena changed"
+    return x
+
+
+def _tsolve_check_bwd(case, x1, what):
+    """The transposed backward launch is the adjoint of the forward launch with unit = 1 and the same interchanges: with M as
+    _solve_check_fwd builds it (kernel_ref.tsolve_matrix) and z the stored x1[blk], column by column
+        M^T z + Lb^T x0[gi] = x0[blk],   nterms = the nonzeros of M's column + the rows below,   mag = |M^T| |z| + |Lb^T| |x0[gi]|.
+    Everything in x outside the blocks is bit-unchanged.  Returns the worst err / bound."""
+    x0 = case.x
+    written = np.zeros(x0.shape, dtype=bool)
+    worst = 0.0
+    for p in case.panels:
+        b, z, xr, Lb = p["b"], x1[p["blk"]], x0[p["gi"]], p["Lb"]
+        M = kr.tsolve_matrix(p["D"], p["pos"], NB)
+        worst = max(worst, kr.assert_equations(kr.matmul_ld(M.T, z) + kr.matmul_ld(Lb.T, xr), x0[p["blk"]], (M != 0).sum(0) + p["below"],
+                                               kr.matmul_ld(np.abs(M.T), np.abs(z)) + kr.matmul_ld(np.abs(Lb.T), np.abs(xr)), case.cols,
+                                               f"{what} b={b} below={p['below']}"))
+        written[p["blk"]] = True
+    kr.assert_unchanged(x0, x1, written, what)
+    return worst
 
 
 def _solve_name(width, direction, big=None):
