@@ -190,6 +190,33 @@ int sf_chol_plan_residual_weights(sf_chol_plan *plan, sf_float *w_host);
  * Stats: "last_condest_solves" (sweep pairs run), "last_condest_ms" (device time from the first to the last kernel, the waits for
  * the host's decisions included), "bytes_condest" (2 n + 2 doubles kept after the first call, not in "bytes_device"). */
 int sf_chol_plan_condest(sf_chol_plan *plan, sf_float *anorm, sf_float *ainv_norm_est);
+/* The two halves of the solve on their own, with the resident factor L (A = L L^T of the permuted matrix), permuted space:
+ * X <- L^{-1} B (SF_HALF_L, the forward sweep: whitening) or X <- L^{-T} B (SF_HALF_LT, the backward sweep); SF_HALF_L and then
+ * SF_HALF_LT is sf_chol_plan_solve_many.  B, X: column-major host arrays, leading dimensions ldb, ldx >= max(n, 1); X may be B
+ * (ldx == ldb).  nrhs == 0: no-op.  nrhs == 1 runs the one-column kernels of sf_chol_plan_solve, nrhs > 1 the 16-wide ones of
+ * sf_chol_plan_solve_many in chunks of 16 (its device block, allocated by whichever call comes first: "bytes_solve_many"; SF_ERR_ALLOC
+ * leaves the plan usable).  Whole, resident Cholesky plans only (schedule-only, partial, sharded, mapped, out-of-core and LU plans:
+ * SF_ERR_ARG), and like sf_chol_plan_refine refused (SF_ERR_ARG) when the last factorization that was started has not succeeded.
+ * "last_half_ms": device time of the sweeps of the last call, copies excluded. */
+#define SF_HALF_L  0   /* X <- L^{-1} B   (forward sweep only)  */
+#define SF_HALF_LT 1   /* X <- L^{-T} B   (backward sweep only) */
+int sf_chol_plan_solve_half(sf_chol_plan *plan, int which, sf_long nrhs,
+                            const sf_float *B, sf_long ldb, sf_float *X, sf_long ldx);
+/* q[j] = b_j^T A^{-1} b_j = |L^{-1} b_j|_2^2 for j < nrhs (the Mahalanobis term of a Gaussian log-density; with sf_chol_plan_logdet
+ * the log-likelihood): the forward sweep and a per-column sum of squares on the device, two passes in a fixed order without
+ * floating-point atomics -- a NaN or Inf stays in its column, a zero column gives exactly 0.  Only q (nrhs doubles) comes back.
+ * B, plans, kernels and chunking as sf_chol_plan_solve_half.  "last_quadform_ms": device time of the last call, copies excluded. */
+int sf_chol_plan_quadform(sf_chol_plan *plan, sf_long nrhs, const sf_float *B, sf_long ldb, sf_float *q);
+/* Gaussian sampling with precision matrix A: X[:, j] = L^{-T} z_j with z_j ~ N(0, I) generated on the device, so Cov(x) = A^{-1}
+ * (permuted space); Z != NULL also returns the normals used (X, Z: column-major host arrays, ldx, ldz >= max(n, 1); Z != X).
+ * Column j is sample number s = first_sample + j of the stream `seed`: element (i, s) depends on (seed, i, s) alone, never on
+ * nsamples or on how a run is cut into calls.  Philox4x32-10 with the counter (i lo, i hi, p lo, p hi), p = s >> 1, and the key
+ * (seed lo, seed hi) gives r0..r3; u1 = ((r0 >> 5) * 2^26 + (r1 >> 6) + 0.5) * 2^-53, u2 likewise from r2, r3; Box-Muller:
+ * rad = sqrt(-2 log u1), th = 2 pi u2, the normal is rad cos(th) for even s and rad sin(th) for odd s.  nsamples == 0: no-op.
+ * Always the 16-wide kernels (the block is generated in their layout).  Plans as sf_chol_plan_solve_half.  "last_sample_ms":
+ * device time of the last call (generator and sweeps), copies excluded. */
+int sf_chol_plan_sample(sf_chol_plan *plan, sf_long nsamples, uint64_t seed, uint64_t first_sample,
+                        sf_float *X, sf_long ldx, sf_float *Z /* or NULL */, sf_long ldz);
 /* statistics: "levels","launches","gemm_tasks","update_pairs","flops_exec","flops_update",
  * "scatter_elems","bytes_device","last_ms" (device time of the last factorize, HIP events),
  * "last_update_ms","last_panel_ms","last_load_ms" (only when profiling is on) */

@@ -86,6 +86,12 @@ lib.sf_chol_plan_solve.argtypes = [C.c_void_p, c_double_p, c_double_p]
 lib.sf_chol_plan_solve.restype = C.c_int
 lib.sf_chol_plan_solve_many.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64]
 lib.sf_chol_plan_solve_many.restype = C.c_int
+lib.sf_chol_plan_solve_half.argtypes = [C.c_void_p, C.c_int, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64]
+lib.sf_chol_plan_solve_half.restype = C.c_int
+lib.sf_chol_plan_quadform.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, c_double_p]
+lib.sf_chol_plan_quadform.restype = C.c_int
+lib.sf_chol_plan_sample.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, c_double_p, C.c_int64, c_double_p, C.c_int64]
+lib.sf_chol_plan_sample.restype = C.c_int
 lib.sf_chol_plan_selinv.argtypes = [C.c_void_p]
 lib.sf_chol_plan_selinv.restype = C.c_int
 lib.sf_chol_plan_get_selinv_range.argtypes = [C.c_void_p, C.c_int64, C.c_int64, c_double_p]

@@ -530,6 +530,51 @@ class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, 
         """X = A^-1 B for an (n, k) block of right-hand sides (any memory order), permuted space, 16 columns per device sweep"""
         return _solve_many(lib.sf_chol_plan_solve_many, "sf_chol_plan_solve_many", self._h, self.n, B)
 
+    def _block(self, B, what):
+        """1-D or (n, k) input in any memory order -> (column-major float64 (n, k), was 1-D)"""
+        B = np.asarray(B)
+        one = B.ndim == 1
+        if one:
+            B = B.reshape(-1, 1)
+        if B.ndim != 2 or B.shape[0] != self.n:
+            raise ValueError(f"{what}: B must have shape ({self.n},) or ({self.n}, k), got {B.shape}")
+        return np.asfortranarray(B, dtype=np.float64), one
+
+    def solve_half(self, B, which="L"):
+        """one half of the solve with the resident factor L (A = L L^T, permuted space): L^-1 B (which="L", whitening) or
+        L^-T B (which="Lt"); "L" then "Lt" is solve_many.  B: (n,) or (n, k) in any memory order"""
+        if which not in ("L", "Lt"):
+            raise ValueError(f"solve_half: which must be 'L' or 'Lt', got {which!r}")
+        Bf, one = self._block(B, "solve_half")
+        k, ld = Bf.shape[1], max(self.n, 1)
+        X = np.empty((self.n, k), dtype=np.float64, order="F")
+        if k:
+            check(lib.sf_chol_plan_solve_half(self._h, 0 if which == "L" else 1, k, _dp(Bf), ld, _dp(X), ld), "sf_chol_plan_solve_half")
+        return X[:, 0] if one else X
+
+    def quadform(self, B):
+        """b^T A^-1 b = |L^-1 b|^2, reduced on the device: a float for a 1-D b, an array of k values for an (n, k) block"""
+        Bf, one = self._block(B, "quadform")
+        k = Bf.shape[1]
+        q = np.zeros(max(k, 1), dtype=np.float64)
+        if k:
+            check(lib.sf_chol_plan_quadform(self._h, k, _dp(Bf), max(self.n, 1), _dp(q)), "sf_chol_plan_quadform")
+        return float(q[0]) if one else q[:k]
+
+    def sample(self, k, seed=0, first=0, return_z=False):
+        """k samples x ~ N(0, A^-1) as the columns of an (n, k) array (permuted space): x = L^-T z with the standard normals z
+        generated on the device.  Column j is sample first + j of the stream `seed`, whatever k is and however a run is cut
+        into calls.  return_z: (X, Z) with the normals used"""
+        k, ld = int(k), max(self.n, 1)
+        if k < 0:
+            raise ValueError("sample: k must not be negative")
+        X = np.empty((self.n, k), dtype=np.float64, order="F")
+        Z = np.empty((self.n, k), dtype=np.float64, order="F") if return_z else None
+        if k:
+            check(lib.sf_chol_plan_sample(self._h, k, int(seed), int(first), _dp(X), ld, _dp(Z) if return_z else None, ld),
+                  "sf_chol_plan_sample")
+        return (X, Z) if return_z else X
+
     def selinv(self):
         """selected inversion: A^-1 on the pattern of L into a device arena (permuted space), from the resident factor"""
         check(lib.sf_chol_plan_selinv(self._h), "sf_chol_plan_selinv")

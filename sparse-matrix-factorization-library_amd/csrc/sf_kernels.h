@@ -218,6 +218,14 @@ void launch_condest_argmax_next(double* x, int64_t n, CondScalars* s, int first,
 void launch_solve_many_pack(const double* Bc, int64_t n, int cw, double* X, hipStream_t st);
 void launch_solve_many_unpack(const double* X, int64_t n, int cw, double* Bc, hipStream_t st);
 
+// ---- half solves, quadratic forms, sampling (sf_sample.hip; the sweeps are the launchers above) ----
+// X[i][c] = the standard normal (i, s0 + c) of the stream `seed` for c < cw, 0 for cw <= c < SVM_W: the row-major n x SVM_W block
+void launch_sample_fill(double* X, int64_t n, int cw, uint64_t seed, uint64_t s0, hipStream_t st);
+// per-column sums of squares of the row-major n x width block X (width 1 or SVM_W), two passes in a fixed order; scratch:
+// QF_MAXB x width parts, then the `width` results
+constexpr int QF_MAXB = 1024;
+void launch_quadform(const double* X, int64_t n, int width, double* scratch, hipStream_t st);
+
 // ---- selected inversion (sf_selinv.hip, sf_chol_plan_selinv) ----
 // one unit: columns [cb, cb + w) of the supernode whose panel starts at lx (factor and arena share the layout), rows at Lsi[rows ..]
 struct SelUnit {

@@ -264,6 +264,10 @@ struct sf_chol_plan {
     double* d_xm = nullptr;
     size_t bytes_solve_many = 0;
     double last_solve_many_ms = 0;
+    // sf_chol_plan_solve_half / _quadform / _sample (sf_sample.hip): d_x or d_xm as above; d_qf = the parts and the results of the
+    // per-column sums of squares, a fixed size allocated by the first quadform call (in no byte count)
+    double* d_qf = nullptr;
+    double last_half_ms = 0, last_quadform_ms = 0, last_sample_ms = 0;
     // sf_chol_plan_selinv (sf_selinv.hip).  Generations of the factor: factor_gen moves whenever the values or the resident factor
     // change (set_values, the start of a factorization, an import); fact_gen = factor_gen of the last factorization started,
     // ok_gen = that of the last one that succeeded (sf_chol_plan_sync) or of an import; sel_gen = factor_gen the arena was computed from
