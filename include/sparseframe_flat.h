@@ -217,6 +217,53 @@ int sf_chol_plan_quadform(sf_chol_plan *plan, sf_long nrhs, const sf_float *B, s
  * device time of the last call (generator and sweeps), copies excluded. */
 int sf_chol_plan_sample(sf_chol_plan *plan, sf_long nsamples, uint64_t seed, uint64_t first_sample,
                         sf_float *X, sf_long ldx, sf_float *Z /* or NULL */, sf_long ldz);
+/* ---- device-pointer entry points: right-hand sides, solutions, samples and matrix values that stay on the device,
+ * optionally in the caller's own numbering.  Whole, resident plans only (schedule-only, partial, sharded, mapped and out-of-core
+ * plans: SF_ERR_ARG, as sf_chol_plan_solve_many).
+ * Synchronisation: the work runs on the plan's stream and every call returns after its result is complete.  The caller must have
+ * completed whatever produces the device arrays it passes, or run the plan on the producers' stream (sf_chol_plan_set_stream).
+ * There is no asynchronous variant.
+ * Pointers: every device pointer is checked with hipPointerGetAttributes before anything is enqueued -- one that is not device
+ * (or managed) memory of the plan's device, or whose allocation ends before the block does, is SF_ERR_ARG. ---- */
+/* the ordering for SF_DEV_PERM_IN / SF_DEV_PERM_OUT and sf_chol_plan_permute_device: perm[new] = old, n entries, as
+ * sf_symbolic_create takes it (NULL: the identity).  Not a permutation of 0..n-1: SF_ERR_ARG, the plan keeps what it had.  Uploaded
+ * as 32-bit indices, like the plan's own row lists; stat "bytes_ordering" (with the value map's bytes, not in "bytes_device").
+ * Cholesky and LU plans. */
+int sf_chol_plan_set_ordering(sf_chol_plan *plan, const sf_long *perm);
+#define SF_OP_SOLVE   0   /* X <- A^{-1} B                                   (Cholesky and LU plans) */
+#define SF_OP_HALF_L  1   /* X <- L^{-1} B, as SF_HALF_L                     (Cholesky plans)        */
+#define SF_OP_HALF_LT 2   /* X <- L^{-T} B, as SF_HALF_LT                    (Cholesky plans)        */
+#define SF_OP_TRANS   3   /* X <- A^{-T} B, as sf_lu_plan_solve_transposed   (LU plans)              */
+#define SF_DEV_PERM_IN  1 /* row i of the block the sweeps see is row perm[i] of dB: dB is in the caller's numbering */
+#define SF_DEV_PERM_OUT 2 /* row i of the result goes to row perm[i] of dX: dX is in the caller's numbering          */
+/* sf_chol_plan_solve / _solve_many / _solve_half on device memory.  dB, dX: column-major device arrays, ldb, ldx >= max(n, 1);
+ * dX == dB with ldx == ldb is allowed, the flags included (a chunk is loaded whole before any of it is stored).  With P the
+ * ordering, the sweeps run on (PERM_IN ? P dB : dB) and dX receives (PERM_OUT ? P^T : I) times their result: both flags on
+ * SF_OP_SOLVE solve the caller's own system.  A flag without sf_chol_plan_set_ordering, an op the plan kind does not have, a
+ * plan whose last started factorization has not succeeded: SF_ERR_ARG.  nrhs == 1 runs the one-column kernels on the plan's
+ * vector, nrhs > 1 the 16-wide ones in chunks ("bytes_solve_many", allocated by whichever call comes first).  A block moves
+ * straight between the caller's memory and the plan's: no staging copy.  Stats: "last_solve_ms" (nrhs == 1), "last_solve_many_ms"
+ * (SF_OP_SOLVE, SF_OP_TRANS with nrhs > 1), "last_half_ms" (the halves): device time from the first to the last kernel of the
+ * call, the load and store kernels included. */
+int sf_chol_plan_solve_device(sf_chol_plan *plan, int op, int flags, sf_long nrhs,
+                              const sf_float *dB, sf_long ldb, sf_float *dX, sf_long ldx);
+/* the ordering alone: dX = P dB (row i = row perm[i] of dB), or with inverse != 0 dX = P^T dB (row perm[i] = row i of dB).  Not in
+ * place (dX == dB: SF_ERR_ARG).  Needs sf_chol_plan_set_ordering, no factorization.  Cholesky and LU plans. */
+int sf_chol_plan_permute_device(sf_chol_plan *plan, int inverse, sf_long nrhs,
+                                const sf_float *dB, sf_long ldb, sf_float *dX, sf_long ldx);
+/* sf_chol_plan_sample with the samples stored into device memory (flags: 0 or SF_DEV_PERM_OUT); the same generator and stream
+ * definition, so column j holds what sf_chol_plan_sample gives for the same (seed, first_sample + j).  No Z output. */
+int sf_chol_plan_sample_device(sf_chol_plan *plan, sf_long nsamples, uint64_t seed, uint64_t first_sample, int flags,
+                               sf_float *dX, sf_long ldx);
+/* sf_chol_plan_set_values from device memory (nnz doubles): a device-to-device copy with the same effects on the plan */
+int sf_chol_plan_set_values_device(sf_chol_plan *plan, const sf_float *dLx);
+/* values straight from the caller's own value array: map[p] in [-1, nsrc) for every entry p of Lx (mapU: of Ux, LU plans with an
+ * unsymmetric input, else NULL) is the position of that entry in an array of nsrc doubles, -1 an entry the caller does not supply
+ * (value 0).  Validated (SF_ERR_ARG, the plan keeps what it had) and uploaded once ("bytes_ordering");
+ * sf_chol_plan_set_values_mapped_device(dAx) is then one gather kernel per time step with every effect of set_values.  Cholesky
+ * and LU plans. */
+int sf_chol_plan_set_value_map(sf_chol_plan *plan, sf_long nsrc, const sf_long *mapL, const sf_long *mapU /* or NULL */);
+int sf_chol_plan_set_values_mapped_device(sf_chol_plan *plan, const sf_float *dAx);
 /* statistics: "levels","launches","gemm_tasks","update_pairs","flops_exec","flops_update",
  * "scatter_elems","bytes_device","last_ms" (device time of the last factorize, HIP events),
  * "last_update_ms","last_panel_ms","last_load_ms" (only when profiling is on) */
@@ -441,6 +488,17 @@ int sf_lu_plan_solve_many(sf_lu_plan *plan, sf_long nrhs, const sf_float *B, sf_
  * plan whose last started factorization has not succeeded (as sf_lu_plan_refine). */
 int sf_lu_plan_solve_transposed(sf_lu_plan *plan, const sf_float *b_host, sf_float *x_host);
 int sf_lu_plan_solve_many_transposed(sf_lu_plan *plan, sf_long nrhs, const sf_float *B, sf_long ldb, sf_float *X, sf_long ldx);
+/* the device-pointer entry points for an LU plan (see sf_chol_plan_set_ordering and below): op is SF_OP_SOLVE or SF_OP_TRANS, both with
+ * the plan's interchanges when pivoting is on; set_values_device takes dUx as sf_lu_plan_set_values takes Ux (NULL when U aliases
+ * L) and finds max |a_ij|, the scale of the pivot perturbation, on the device.  A Cholesky plan is refused (SF_ERR_ARG). */
+int sf_lu_plan_set_ordering(sf_lu_plan *plan, const sf_long *perm);
+int sf_lu_plan_solve_device(sf_lu_plan *plan, int op, int flags, sf_long nrhs,
+                            const sf_float *dB, sf_long ldb, sf_float *dX, sf_long ldx);
+int sf_lu_plan_permute_device(sf_lu_plan *plan, int inverse, sf_long nrhs,
+                              const sf_float *dB, sf_long ldb, sf_float *dX, sf_long ldx);
+int sf_lu_plan_set_values_device(sf_lu_plan *plan, const sf_float *dLx, const sf_float *dUx /* or NULL */);
+int sf_lu_plan_set_value_map(sf_lu_plan *plan, sf_long nsrc, const sf_long *mapL, const sf_long *mapU /* or NULL */);
+int sf_lu_plan_set_values_mapped_device(sf_lu_plan *plan, const sf_float *dAx);
 /* sf_chol_plan_condest for an LU plan (pivoting on or off); a Cholesky plan is refused (SF_ERR_ARG) */
 int sf_lu_plan_condest(sf_lu_plan *plan, sf_float *anorm, sf_float *ainv_norm_est);
 /* sf_chol_plan_residual / sf_chol_plan_refine for an LU plan (the solves apply the plan's pivots when pivoting is on); a Cholesky

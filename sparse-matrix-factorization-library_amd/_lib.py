@@ -140,6 +140,28 @@ lib.sf_chol_plan_residual_weights.restype = C.c_int
 for _n in ("sf_chol_plan_refine", "sf_lu_plan_refine"):
     getattr(lib, _n).argtypes = [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_double, c_double_p]
     getattr(lib, _n).restype = C.c_int
+# device-pointer entry points (sf_device_io.hip): device addresses travel as integers
+for _n in ("sf_chol_plan_set_ordering", "sf_lu_plan_set_ordering"):
+    getattr(lib, _n).argtypes = [C.c_void_p, c_long_p]
+    getattr(lib, _n).restype = C.c_int
+for _n in ("sf_chol_plan_solve_device", "sf_lu_plan_solve_device"):
+    getattr(lib, _n).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+    getattr(lib, _n).restype = C.c_int
+for _n in ("sf_chol_plan_permute_device", "sf_lu_plan_permute_device"):
+    getattr(lib, _n).argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+    getattr(lib, _n).restype = C.c_int
+lib.sf_chol_plan_sample_device.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_int64]
+lib.sf_chol_plan_sample_device.restype = C.c_int
+lib.sf_chol_plan_set_values_device.argtypes = [C.c_void_p, C.c_void_p]
+lib.sf_chol_plan_set_values_device.restype = C.c_int
+lib.sf_lu_plan_set_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+lib.sf_lu_plan_set_values_device.restype = C.c_int
+for _n in ("sf_chol_plan_set_value_map", "sf_lu_plan_set_value_map"):
+    getattr(lib, _n).argtypes = [C.c_void_p, C.c_int64, c_long_p, c_long_p]
+    getattr(lib, _n).restype = C.c_int
+for _n in ("sf_chol_plan_set_values_mapped_device", "sf_lu_plan_set_values_mapped_device"):
+    getattr(lib, _n).argtypes = [C.c_void_p, C.c_void_p]
+    getattr(lib, _n).restype = C.c_int
 lib.sf_chol_plan_stat.argtypes = [C.c_void_p, C.c_char_p]
 lib.sf_chol_plan_stat.restype = C.c_double
 lib.sf_chol_plan_set_profiling.argtypes = [C.c_void_p, C.c_int]

@@ -97,6 +97,7 @@ class Symbolic:
         self._h = h
         self._cache = {}
         self.dev_slot_size = dev_slot_size
+        self._input = (n, Cp, Ci, perm, bool(symmetric))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -126,6 +127,25 @@ class Symbolic:
                                      if ln.value else np.zeros(0))
             return self._cache[name]
         raise AttributeError(name)
+
+    def value_map(self):
+        """(nsrc, mapL, mapU) for set_value_map: mapL[p] (mapU[p]) is the position in the caller's own value array Cx -- the one
+        this analysis was given, nsrc = Cp[n] entries -- that entry p of Lx (Ux) is taken from, or -1 for an entry the caller does
+        not supply (value 0); mapU is None unless this is an LU analysis of an unsymmetric input.  So Lx == where(mapL >= 0,
+        Cx[mapL], 0) for ANY values on the same pattern; an entry given more than once follows the analysis' own rule.
+        Costs one more analysis: the pattern is analysed again with the values 1, 2, ..., nsrc (exact in fp64 below 2^53) and
+        the positions are read off the resulting Lx / Ux."""
+        n, Cp, Ci, perm, symmetric = self._input
+        nsrc = int(Cp[n]) if n > 0 else 0
+        if nsrc >= 1 << 53:
+            raise ValueError("value_map: more than 2^53 entries")
+        tag = np.zeros(len(Ci), dtype=np.float64)
+        tag[:nsrc] = 1.0 + np.arange(nsrc, dtype=np.float64)
+        twin = Symbolic(n, Cp, Ci, tag, perm, self.dev_slot_size, self.method, symmetric)
+        mapL = np.rint(twin.Lx).astype(np.int64) - 1
+        mapU = np.rint(twin.Ux).astype(np.int64) - 1 if self.method == "lu" and not symmetric else None
+        twin.close()
+        return nsrc, mapL, mapU
 
     @property
     def flops_struct(self):
@@ -452,7 +472,144 @@ class _CondestMixin:
         return (anorm.value, ainv.value) if return_parts else anorm.value * ainv.value
 
 
-class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin):
+_DEV_OPS = {"solve": 0, "half_L": 1, "half_Lt": 2, "trans": 3}
+
+
+def _dev_tensor(T, rows, device, what, writable=False):
+    """checks a device tensor (anything with data_ptr(), dtype, shape, stride(), is_cuda and device: a torch tensor) and returns
+    (tensor to pass, columns, leading dimension, was 1-D).  float64, on the plan's device, 1-D of `rows` entries or 2-D
+    (rows, k) with unit stride along the rows, i.e. column-major.  A C-contiguous 2-D INPUT is taken via .t().contiguous().t()
+    (one device copy); an output must be column-major already."""
+    for attr in ("data_ptr", "dtype", "shape", "stride", "is_cuda", "device"):
+        if not hasattr(T, attr):
+            raise TypeError(f"{what}: expected a device tensor (missing .{attr}), got {type(T).__name__}")
+    if not str(T.dtype).endswith("float64"):
+        raise TypeError(f"{what}: tensor must be float64, got {T.dtype}")
+    if not T.is_cuda:
+        raise ValueError(f"{what}: tensor must live on the device, got device {T.device}")
+    if getattr(T.device, "index", None) != device:
+        raise ValueError(f"{what}: tensor is on {T.device}, the plan on device {device}")
+    shape, one = tuple(T.shape), len(T.shape) == 1
+    if len(shape) not in (1, 2) or shape[0] != rows:
+        raise ValueError(f"{what}: tensor must have shape ({rows},) or ({rows}, k), got {shape}")
+    k = 1 if one else shape[1]
+    st = tuple(T.stride())
+    ldmin = max(rows, 1)
+    ok = (rows <= 1 or st[0] == 1) and (one or k <= 1 or st[1] >= ldmin)
+    if not ok:
+        if writable or one or st[1] != 1 or st[0] != k:
+            raise ValueError(f"{what}: tensor must be column-major (unit stride along the rows), got strides {st}")
+        T = T.t().contiguous().t()
+        st = tuple(T.stride())
+    ld = ldmin if (one or k <= 1) else st[1]
+    return T, k, ld, one
+
+
+class _DeviceIOMixin:
+    """right-hand sides, solutions, samples and matrix values that stay on the device (sf_*_plan_*_device).  The
+    arguments are torch tensors on the plan's device; torch is imported by these methods only.  Every method waits for the
+    current torch stream of the device before the C call (the tensors' producers) and returns with the result complete."""
+
+    def _dev_fn(self, what):
+        return getattr(lib, ("sf_lu_plan_" if isinstance(self, LUPlan) else "sf_chol_plan_") + what)
+
+    def _dev_sync(self):
+        import torch
+        torch.cuda.current_stream(self.device).synchronize()
+        return torch
+
+    def _dev_out(self, torch, k, one):
+        if one:
+            return torch.empty(self.n, dtype=torch.float64, device=f"cuda:{self.device}")
+        return torch.empty_strided((self.n, k), (1, max(self.n, 1)), dtype=torch.float64, device=f"cuda:{self.device}")
+
+    def set_ordering(self, perm=None):
+        """the ordering perm[new] = old (what analyze was given; None: the identity) for perm_in / perm_out / permute_device"""
+        if perm is not None:
+            perm = _i64(perm)
+            if perm.shape != (self.n,):
+                raise ValueError(f"set_ordering: perm must have shape ({self.n},), got {perm.shape}")
+        fn = self._dev_fn("set_ordering")
+        check(fn(self._h, _lp(perm) if perm is not None else None), fn.__name__)
+
+    def solve_device(self, B, out=None, op="solve", perm_in=False, perm_out=False):
+        """X = op(B) with the resident factor, B and X device tensors ((n,) or column-major (n, k)); out=None allocates X
+        (torch.empty_strided, column-major), out=B solves in place.  op: "solve"; "half_L" / "half_Lt" (CholPlan, as
+        solve_half); "trans" (LUPlan).  perm_in: B is in the caller's numbering (row perm[i] of B is row i of the permuted
+        system); perm_out: so is X.  Both with op="solve" solve the caller's own system A x = b."""
+        lu = isinstance(self, LUPlan)
+        if op not in (("solve", "trans") if lu else ("solve", "half_L", "half_Lt")):
+            raise ValueError(f"solve_device: op {op!r} is not one of this plan's")
+        B, k, ldb, one = _dev_tensor(B, self.n, self.device, "solve_device")
+        torch = None
+        if out is None:
+            torch = self._dev_sync()
+            out = self._dev_out(torch, k, one)
+        X, kx, ldx, onex = _dev_tensor(out, self.n, self.device, "solve_device (out)", writable=True)
+        if (kx, onex) != (k, one):
+            raise ValueError(f"solve_device: out must have the shape of B, got {tuple(out.shape)}")
+        if k and self.n:
+            if torch is None:
+                self._dev_sync()
+            fn = self._dev_fn("solve_device")
+            check(fn(self._h, _DEV_OPS[op], (1 if perm_in else 0) | (2 if perm_out else 0), k, B.data_ptr(), ldb, X.data_ptr(), ldx),
+                  fn.__name__)
+        return out
+
+    def permute_device(self, B, out=None, inverse=False):
+        """out = B[perm] (row i = row perm[i] of B: caller's numbering -> permuted), or with inverse out[perm] = B; not in place"""
+        B, k, ldb, one = _dev_tensor(B, self.n, self.device, "permute_device")
+        torch = None
+        if out is None:
+            torch = self._dev_sync()
+            out = self._dev_out(torch, k, one)
+        X, kx, ldx, onex = _dev_tensor(out, self.n, self.device, "permute_device (out)", writable=True)
+        if (kx, onex) != (k, one):
+            raise ValueError(f"permute_device: out must have the shape of B, got {tuple(out.shape)}")
+        if k and self.n:
+            if torch is None:
+                self._dev_sync()
+            fn = self._dev_fn("permute_device")
+            check(fn(self._h, 1 if inverse else 0, k, B.data_ptr(), ldb, X.data_ptr(), ldx), fn.__name__)
+        return out
+
+    def set_values_device(self, Lx, Ux=None):
+        """set_values from device tensors (1-D float64, nnz / unz entries; Ux: LUPlan with an unsymmetric input)"""
+        lu = isinstance(self, LUPlan)
+        L, _, _, one = _dev_tensor(Lx, self._nnz, self.device, "set_values_device")
+        if not one:
+            raise ValueError("set_values_device: Lx must be 1-D")
+        args = [L.data_ptr() or None]
+        if lu:
+            if self._alias:
+                args.append(None)
+            else:
+                U, _, _, _ = _dev_tensor(Ux, self._unz, self.device, "set_values_device (Ux)")
+                args.append(U.data_ptr() or None)
+        self._dev_sync()
+        fn = self._dev_fn("set_values_device")
+        check(fn(self._h, *args), fn.__name__)
+
+    def set_value_map(self, nsrc, mapL, mapU=None):
+        """(nsrc, mapL, mapU) of Symbolic.value_map(): uploaded once for set_values_mapped_device"""
+        mapL = _i64(mapL)
+        mapU = _i64(mapU) if mapU is not None else None
+        fn = self._dev_fn("set_value_map")
+        check(fn(self._h, int(nsrc), _lp(mapL), _lp(mapU) if mapU is not None else None), fn.__name__)
+        self._nsrc = int(nsrc)
+
+    def set_values_mapped_device(self, Ax):
+        """set_values from the caller's own value array on the device (1-D float64, nsrc entries, the entry order analyze was
+        given): one gather kernel through the map of set_value_map"""
+        if getattr(self, "_nsrc", None) is None:
+            raise ValueError("set_values_mapped_device: no value map (set_value_map)")
+        A, _, _, _ = _dev_tensor(Ax, self._nsrc, self.device, "set_values_mapped_device")
+        self._dev_sync()
+        fn = self._dev_fn("set_values_mapped_device")
+        check(fn(self._h, A.data_ptr() or None), fn.__name__)
+
+
+class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin, _DeviceIOMixin):
     """Device-resident supernodal Cholesky (flat ABI).  Raises if no HIP device is present.
     phase/load_top: multi-GPU sharding (sf_chol_plan_create_sharded); default = the whole matrix on one device.
     rank/nranks (with phase): distributed top (sf_chol_plan_create_distributed), run with factorize_phase(0) and then
@@ -491,6 +648,7 @@ class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, 
         self._h = h
         self.xsize = sym.xsize
         self.n = sym.n
+        self._nnz = int(self._keep[5][-1]) if len(self._keep[5]) else 0        # Lp[n]
 
     def set_values(self, Lx):
         Lx = _f64(Lx)
@@ -575,6 +733,23 @@ class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, 
                   "sf_chol_plan_sample")
         return (X, Z) if return_z else X
 
+    def sample_device(self, k, seed=0, first=0, out=None, perm_out=False):
+        """sample(k, seed, first) with the samples stored into a device tensor (out, column-major (n, k), or a new one);
+        perm_out: in the caller's numbering (set_ordering).  The same stream of samples as sample()"""
+        k = int(k)
+        if k < 0:
+            raise ValueError("sample_device: k must not be negative")
+        torch = self._dev_sync()
+        if out is None:
+            out = self._dev_out(torch, k, False)
+        X, kx, ldx, one = _dev_tensor(out, self.n, self.device, "sample_device (out)", writable=True)
+        if one or kx != k:
+            raise ValueError(f"sample_device: out must have shape ({self.n}, {k}), got {tuple(out.shape)}")
+        if k and self.n:
+            check(lib.sf_chol_plan_sample_device(self._h, k, int(seed), int(first), 2 if perm_out else 0, X.data_ptr(), ldx),
+                  "sf_chol_plan_sample_device")
+        return out
+
     def selinv(self):
         """selected inversion: A^-1 on the pattern of L into a device arena (permuted space), from the resident factor"""
         check(lib.sf_chol_plan_selinv(self._h), "sf_chol_plan_selinv")
@@ -613,7 +788,7 @@ class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, 
         self.close()
 
 
-class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin):
+class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin, _DeviceIOMixin):
     """Device-resident supernodal no-pivot LU (flat ABI, sf_lu_plan_*).  `sym` comes from analyze(..., method='lu').
     phase/load_top/rank/nranks: distributed multi-GPU plan (sf_lu_plan_create_distributed), as CholPlan."""
 
@@ -646,6 +821,8 @@ class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _C
         self._h = h
         self.xsize = sym.xsize
         self.n = sym.n
+        self._nnz = int(self._keep[5][-1]) if len(self._keep[5]) else 0        # Lp[n]
+        self._unz = 0 if self._alias or not len(self._keep[7]) else int(self._keep[7][-1])      # Up[n]
 
     def set_values(self, Lx, Ux=None):
         Lx = _f64(Lx)

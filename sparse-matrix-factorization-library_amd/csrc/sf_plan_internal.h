@@ -142,6 +142,9 @@ bool sf_factor_usable(sf_chol_plan* p);
 // *d_anorm = device address of |A|_1 of the plan's CURRENT values, up to date on `st` (the residual's row / column form is set up by
 // the first call, the norm recomputed when factor_gen has moved); the plans sf_chol_plan_residual accepts
 int sf_refine_anorm(sf_chol_plan* p, const double** d_anorm, hipStream_t st);
+// ---- shared with the device-pointer solves (sf_device_io.hip) ----
+// x <- A^{-T} x for an LU plan (sf_solve_t.hip; the caller has zeroed the sync block on the stream)
+void tsolve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, hipStream_t st);
 
 struct sf_chol_plan {
     // ---- overlapped download schedule (built once) and the state of a running download ----
@@ -268,6 +271,13 @@ struct sf_chol_plan {
     // per-column sums of squares, a fixed size allocated by the first quadform call (in no byte count)
     double* d_qf = nullptr;
     double last_half_ms = 0, last_quadform_ms = 0, last_sample_ms = 0;
+    // sf_*_plan_set_ordering / _set_value_map (sf_device_io.hip): perm[new] = old as 32-bit indices (as d_Lsi), the value map
+    // (nnz entries for Lx, then unz for Ux) and the parts of the LU plans' max |a_ij|; bytes_ordering is not in bytes_device
+    int32_t* d_perm = nullptr;
+    int64_t* d_vmap = nullptr;
+    int64_t vmap_nsrc = 0;
+    double* d_dio_part = nullptr;
+    size_t bytes_ordering = 0;
     // sf_chol_plan_selinv (sf_selinv.hip).  Generations of the factor: factor_gen moves whenever the values or the resident factor
     // change (set_values, the start of a factorization, an import); fact_gen = factor_gen of the last factorization started,
     // ok_gen = that of the last one that succeeded (sf_chol_plan_sync) or of an import; sel_gen = factor_gen the arena was computed from

@@ -445,6 +445,8 @@ bool tsolve_refused(const sf_chol_plan* p) {
     return p->dry || p->partial || p->nranks > 1 || p->ooc_groups > 1 || (p->nsuper > 0 && !p->d_solve);
 }
 
+}  // namespace
+
 // x <- A^{-T} x for an LU plan (the caller has zeroed the sync block on the stream).  The row-major copies of the top steps'
 // diagonal blocks (d_solveT) are made from the PL base here, on every call that asks for them; their diagonal entries are copied
 // too and simply not read.  sf_solve_sweep_bwd remakes them from PU at the start of every solve / solve_many / refine call, so
@@ -479,6 +481,8 @@ void tsolve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, h
         }
     }
 }
+
+namespace {
 
 int condest(sf_chol_plan* p, sf_float* anorm, sf_float* ainv_norm_est) {
     if (tsolve_refused(p) || !p->values_set) return SF_ERR_ARG;
