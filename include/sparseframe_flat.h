@@ -264,6 +264,29 @@ int sf_chol_plan_set_values_device(sf_chol_plan *plan, const sf_float *dLx);
  * and LU plans. */
 int sf_chol_plan_set_value_map(sf_chol_plan *plan, sf_long nsrc, const sf_long *mapL, const sf_long *mapU /* or NULL */);
 int sf_chol_plan_set_values_mapped_device(sf_chol_plan *plan, const sf_float *dAx);
+/* ---- the dense Schur complement of a border: G = B^T A^{-1} B for an n x k block B, permuted space.  With A = L L^T
+ * and Y = L^{-1} B, G = Y^T Y: one FORWARD sweep per chunk of 16 columns (the kernels of sf_chol_plan_solve_half), Y kept on the
+ * device, a v_mfma_f64_16x16x4_f64 reduction over the rows, and only k x k doubles come back.  The diagonal of G is what
+ * sf_chol_plan_quadform returns; k == 1 runs quadform's own one-column path, so G[0] is exactly its value.
+ * B: column-major, ldb >= max(n, 1); G: column-major k x k, ldg >= max(k, 1), written in full (both triangles).  k == 0: SF_OK,
+ * nothing written.  NULL pointers, k < 0, k > SF_GRAM_MAX_K, a short leading dimension: SF_ERR_ARG, nothing written; plans as
+ * sf_chol_plan_quadform (LU, schedule-only, partial, sharded, mapped and out-of-core plans and a plan whose last started
+ * factorization has not succeeded: SF_ERR_ARG).
+ * Determinism: no floating-point atomics and a fixed summation order in the reduction, so for a given Y the result repeats bit
+ * for bit (Y itself repeats to rounding only where the sweep scatters with atomics); G is bit-for-bit symmetric; entry (i, j) is a
+ * function of the columns i and j of B alone, so a NaN or Inf in column j reaches row j and column j of G and nothing else.
+ * The Y store (ceil(k / 16) blocks of n x 16 doubles, the parts of the reduction and the host call's k x k result block) is
+ * allocated or grown by the first call that needs it and kept: stat "bytes_gram", not in "bytes_device"; SF_ERR_ALLOC leaves the
+ * plan as it was.  Stats: "last_gram_ms" (device time of the sweeps and reductions of the last call, copies excluded),
+ * "last_gram_parts" (row slabs, i.e. workgroups per 16 x 16 tile, of the last call; 0 for k == 1). ---- */
+#define SF_GRAM_MAX_K 1024
+int sf_chol_plan_gram(sf_chol_plan *plan, sf_long k, const sf_float *B, sf_long ldb,
+                      sf_float *G, sf_long ldg);            /* host, column-major */
+/* the same on device memory (pointer checks and synchronisation as sf_chol_plan_solve_device; the result is complete on return).
+ * flags: 0 or SF_DEV_PERM_IN (dB is in the caller's numbering; needs sf_chol_plan_set_ordering), any other bit: SF_ERR_ARG.  dG
+ * must not overlap dB (SF_ERR_ARG).  The block goes straight from dB into the Y store: no staging copy. */
+int sf_chol_plan_gram_device(sf_chol_plan *plan, int flags /* 0 | SF_DEV_PERM_IN */, sf_long k,
+                             const sf_float *dB, sf_long ldb, sf_float *dG, sf_long ldg);
 /* statistics: "levels","launches","gemm_tasks","update_pairs","flops_exec","flops_update",
  * "scatter_elems","bytes_device","last_ms" (device time of the last factorize, HIP events),
  * "last_update_ms","last_panel_ms","last_load_ms" (only when profiling is on) */

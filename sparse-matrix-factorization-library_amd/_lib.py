@@ -90,6 +90,10 @@ lib.sf_chol_plan_solve_half.argtypes = [C.c_void_p, C.c_int, C.c_int64, c_double
 lib.sf_chol_plan_solve_half.restype = C.c_int
 lib.sf_chol_plan_quadform.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, c_double_p]
 lib.sf_chol_plan_quadform.restype = C.c_int
+lib.sf_chol_plan_gram.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64]
+lib.sf_chol_plan_gram.restype = C.c_int
+lib.sf_chol_plan_gram_device.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+lib.sf_chol_plan_gram_device.restype = C.c_int
 lib.sf_chol_plan_sample.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, c_double_p, C.c_int64, c_double_p, C.c_int64]
 lib.sf_chol_plan_sample.restype = C.c_int
 lib.sf_chol_plan_selinv.argtypes = [C.c_void_p]

@@ -719,6 +719,88 @@ class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, 
             check(lib.sf_chol_plan_quadform(self._h, k, _dp(Bf), max(self.n, 1), _dp(q)), "sf_chol_plan_quadform")
         return float(q[0]) if one else q[:k]
 
+    GRAM_MAX_K = 1024       # SF_GRAM_MAX_K
+
+    def gram(self, B):
+        """G = B^T A^-1 B, the dense Schur complement of the border B (permuted space): one forward sweep per 16 columns and a
+        reduction on the device, only the (k, k) result comes back.  B: (n, k) in any memory order -> (k, k) float64, bit-for-bit
+        symmetric; a 1-D b -> the float quadform(b).  k <= 1024"""
+        Bf, one = self._block(B, "gram")
+        k = Bf.shape[1]
+        if k > self.GRAM_MAX_K:
+            raise ValueError(f"gram: at most {self.GRAM_MAX_K} columns, got {k}")
+        G = np.zeros((k, k), dtype=np.float64, order="F")
+        if k:
+            check(lib.sf_chol_plan_gram(self._h, k, _dp(Bf), max(self.n, 1), _dp(G), k), "sf_chol_plan_gram")
+        return float(G[0, 0]) if one else G
+
+    def gram_device(self, B, out=None, perm_in=False):
+        """gram(B) for a device tensor B ((n,) or column-major (n, k)) into a device tensor: out (column-major (k, k), not
+        overlapping B) or a new one.  perm_in: B is in the caller's numbering (set_ordering)"""
+        B, k, ldb, one = _dev_tensor(B, self.n, self.device, "gram_device")
+        if k > self.GRAM_MAX_K:
+            raise ValueError(f"gram_device: at most {self.GRAM_MAX_K} columns, got {k}")
+        torch = None
+        if out is None:
+            torch = self._dev_sync()
+            out = torch.empty_strided((k, k), (1, max(k, 1)), dtype=torch.float64, device=f"cuda:{self.device}")
+        G, kg, ldg, oneg = _dev_tensor(out, k, self.device, "gram_device (out)", writable=True)
+        if oneg or kg != k:
+            raise ValueError(f"gram_device: out must have shape ({k}, {k}), got {tuple(out.shape)}")
+        if k:
+            if torch is None:
+                self._dev_sync()
+            check(lib.sf_chol_plan_gram_device(self._h, 1 if perm_in else 0, k, B.data_ptr(), ldb, G.data_ptr(), ldg),
+                  "sf_chol_plan_gram_device")
+        return out
+
+    def schur(self, B, D):
+        """the Schur complement D - B^T A^-1 B of the bordered matrix [[A, B], [B^T, D]] (B: (n, k), D: (k, k))"""
+        Bf, _ = self._block(B, "schur")
+        k = Bf.shape[1]
+        D = np.asarray(D, dtype=np.float64)
+        if D.shape != (k, k):
+            raise ValueError(f"schur: D must have shape ({k}, {k}), got {D.shape}")
+        return D - self.gram(Bf)
+
+    def solve_bordered(self, B, f, g, C=None):
+        """(x, y) with [[A, B], [B^T, -C]] [x; y] = [f; g] (a saddle-point / KKT system; permuted space): B (n, k), f (n,),
+        g (k,), C (k, k) symmetric positive semidefinite or None = 0.  One gram of [B f] gives S0 = B^T A^-1 B and
+        t = B^T A^-1 f; S = C + S0 is factored on the host, y = S^-1 (t - g), x = solve(f - B y): k + 1 forward sweeps and one
+        full solve, no (n, k) block comes back.  A border without full column rank (with C = 0) raises ValueError"""
+        Bf, one = self._block(B, "solve_bordered")
+        k = Bf.shape[1]
+        f = _f64(f)
+        g = np.asarray(g, dtype=np.float64).reshape(-1)
+        if one or f.shape != (self.n,) or g.shape != (k,):
+            raise ValueError(f"solve_bordered: B, f, g must have shapes ({self.n}, k), ({self.n},), (k,), got "
+                             f"{np.shape(B)}, {f.shape}, {g.shape}")
+        if C is not None:
+            C = np.asarray(C, dtype=np.float64)
+            if C.shape != (k, k):
+                raise ValueError(f"solve_bordered: C must have shape ({k}, {k}), got {C.shape}")
+        if k + 1 > self.GRAM_MAX_K:
+            raise ValueError(f"solve_bordered: at most {self.GRAM_MAX_K - 1} border columns, got {k}")
+        G = self.gram(np.column_stack([Bf, f]))
+        S, t = G[:k, :k], G[:k, k]
+        if C is not None:
+            S = S + C
+        y = np.zeros(k)
+        if k:
+            # a pivot that rounding alone could have produced counts as zero: the factorization of an exactly singular S may run
+            # through on a pivot of a few ulps of its diagonal entry, and y would be noise
+            try:
+                R = np.linalg.cholesky(S)
+                singular = bool(np.any(np.diag(R) ** 2 <= 8 * k * np.finfo(np.float64).eps * np.diag(S)))
+            except np.linalg.LinAlgError:
+                singular = True
+            if singular:
+                raise ValueError("solve_bordered: C + B^T A^-1 B is not positive definite: a rank-deficient border "
+                                 "(dependent columns of B where C does not make up for them)")
+            y = np.linalg.solve(R.T, np.linalg.solve(R, t - g))
+        x = self.solve(f - Bf @ y)
+        return x, y
+
     def sample(self, k, seed=0, first=0, return_z=False):
         """k samples x ~ N(0, A^-1) as the columns of an (n, k) array (permuted space): x = L^-T z with the standard normals z
         generated on the device.  Column j is sample first + j of the stream `seed`, whatever k is and however a run is cut

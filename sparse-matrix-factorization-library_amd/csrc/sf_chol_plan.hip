@@ -52,7 +52,7 @@ int sf_chol_plan_destroy(sf_chol_plan* p) {
                     p->d_Up, p->d_Ui, p->d_Ux, p->d_Xp, p->d_pack, p->d_piv, p->d_resid, p->d_loadmask, p->d_loadmapL, p->d_loadmapU, p->d_solve, p->d_solve_sync, p->d_x, p->d_relmap, p->d_scratch, p->d_status, p->d_fill, p->d_solveT, p->d_solveT_list, p->d_xm,
                     p->d_sel, p->d_sel_diag, p->d_sel_units, p->d_sel_pairs, p->d_sel_scratch,
                     p->d_rf_ptr, p->d_rf_col, p->d_rf_pos, p->d_rf_cptr, p->d_rf_ccol, p->d_rf_cpos, p->d_rf_vec, p->d_cond, p->d_qf,
-                    p->d_perm, p->d_vmap, p->d_dio_part};
+                    p->d_perm, p->d_vmap, p->d_dio_part, p->d_gram};
     for (void* q : ptrs)
         if (q && !(q == (void*)p->d_Lsx && p->factor_borrowed)) (void)hipFree(q);      // (a borrowed factor buffer goes back to its lender)
     if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
@@ -1167,6 +1167,9 @@ double sf_chol_plan_stat(const sf_chol_plan* p, const char* name) {
     if (k == "last_quadform_ms") return p->last_quadform_ms;
     if (k == "last_sample_ms") return p->last_sample_ms;
     if (k == "bytes_ordering") return (double)p->bytes_ordering;
+    if (k == "bytes_gram") return (double)p->bytes_gram;
+    if (k == "last_gram_ms") return p->last_gram_ms;
+    if (k == "last_gram_parts") return (double)p->last_gram_parts;
     if (k == "bytes_selinv") return (double)p->bytes_selinv;
     if (k == "last_selinv_ms") return p->last_selinv_ms;
     if (k == "flops_selinv") return p->flops_selinv;

@@ -109,7 +109,7 @@ k_dev_absmax(const double* __restrict__ v, int64_t count, double* __restrict__ p
     if (tid == 0) part[blockIdx.x] = red[0];
 }
 
-static void launch_dev_load1(const double* B, const int32_t* perm, int64_t n, double* x, hipStream_t st) {
+void launch_dev_load1(const double* B, const int32_t* perm, int64_t n, double* x, hipStream_t st) {
     const dim3 g((unsigned)((n + 255) / 256));
     if (perm) hipLaunchKernelGGL(k_dev_load1<true>, g, dim3(256), 0, st, B, perm, n, x);
     else hipLaunchKernelGGL(k_dev_load1<false>, g, dim3(256), 0, st, B, perm, n, x);
@@ -119,7 +119,7 @@ static void launch_dev_store1(const double* x, const int32_t* perm, int64_t n, d
     if (perm) hipLaunchKernelGGL(k_dev_store1<true>, g, dim3(256), 0, st, x, perm, n, X);
     else hipLaunchKernelGGL(k_dev_store1<false>, g, dim3(256), 0, st, x, perm, n, X);
 }
-static void launch_dev_pack(const double* B, int64_t ldb, const int32_t* perm, int64_t n, int cw, double* X, hipStream_t st) {
+void launch_dev_pack(const double* B, int64_t ldb, const int32_t* perm, int64_t n, int cw, double* X, hipStream_t st) {
     const dim3 g((unsigned)((n + DIO_ROWS - 1) / DIO_ROWS));
     if (perm) hipLaunchKernelGGL(k_dev_pack<true>, g, dim3(256), 0, st, B, ldb, perm, n, cw, X);
     else hipLaunchKernelGGL(k_dev_pack<false>, g, dim3(256), 0, st, B, ldb, perm, n, cw, X);
@@ -326,6 +326,9 @@ bool dio_map_ok(const sf_long* map, int64_t count, sf_long nsrc) {
 }
 
 }  // namespace
+
+bool sf_device_ptr_ok(const sf_chol_plan* p, const void* ptr, size_t doubles) { return dio_device_ptr(p, ptr, doubles); }
+int sf_solve_many_block(sf_chol_plan* p) { return dio_block(p); }
 
 extern "C" {
 

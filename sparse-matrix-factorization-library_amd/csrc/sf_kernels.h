@@ -226,6 +226,21 @@ void launch_sample_fill(double* X, int64_t n, int cw, uint64_t seed, uint64_t s0
 constexpr int QF_MAXB = 1024;
 void launch_quadform(const double* X, int64_t n, int width, double* scratch, hipStream_t st);
 
+// ---- device-pointer loads (sf_device_io.hip), shared with sf_gram.hip: perm != nullptr gathers row perm[i] of the caller's block ----
+// x[i] = B[perm ? perm[i] : i]
+void launch_dev_load1(const double* B, const int32_t* perm, int64_t n, double* x, hipStream_t st);
+// the caller's column-major chunk of cw <= SVM_W columns -> the row-major n x SVM_W block X, columns [cw, SVM_W) zero
+void launch_dev_pack(const double* B, int64_t ldb, const int32_t* perm, int64_t n, int cw, double* X, hipStream_t st);
+
+// ---- the Gram matrix Y^T Y of the chunks of a half-solved border (sf_gram.hip, sf_chol_plan_gram) ----
+constexpr int GRAM_SLAB_ROWS = 2048;    // rows of a slab, about
+constexpr int GRAM_MAX_SLABS = 256;     // slabs (workgroups per tile, parts per tile) at most
+// slabs the rows [0, n) are cut into, *slab_rows = rows of each (a multiple of 64); n >= 1
+int gram_slabs(int64_t n, int64_t* slab_rows);
+// chunk row a of G = Y^T Y: the tiles (a, 0 .. a) and their mirrors into the column-major k x k result G (leading dimension ldg).
+// Y: the chunks 0 .. a, chunk c the row-major n x SVM_W block at c * n * SVM_W; part: (a + 1) x gram_slabs x 256 doubles
+void launch_gram_row(const double* Y, int64_t n, int a, int64_t k, double* part, double* G, int64_t ldg, hipStream_t st);
+
 // ---- selected inversion (sf_selinv.hip, sf_chol_plan_selinv) ----
 // one unit: columns [cb, cb + w) of the supernode whose panel starts at lx (factor and arena share the layout), rows at Lsi[rows ..]
 struct SelUnit {

@@ -145,6 +145,13 @@ int sf_refine_anorm(sf_chol_plan* p, const double** d_anorm, hipStream_t st);
 // ---- shared with the device-pointer solves (sf_device_io.hip) ----
 // x <- A^{-T} x for an LU plan (sf_solve_t.hip; the caller has zeroed the sync block on the stream)
 void tsolve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, hipStream_t st);
+// ---- shared with the Gram matrix (sf_gram.hip) ----
+// `ptr` is device (or managed) memory of the plan's device with room for `doubles` doubles from there on (sf_device_io.hip)
+bool sf_device_ptr_ok(const sf_chol_plan* p, const void* ptr, size_t doubles);
+// the n x SVM_W block d_xm with its staging half, allocated by whichever call comes first (sf_device_io.hip)
+int sf_solve_many_block(sf_chol_plan* p);
+// the parts and results of launch_quadform, d_qf, allocated by the first call that needs them (sf_sample.hip)
+int sf_quadform_scratch(sf_chol_plan* p);
 
 struct sf_chol_plan {
     // ---- overlapped download schedule (built once) and the state of a running download ----
@@ -271,6 +278,14 @@ struct sf_chol_plan {
     // per-column sums of squares, a fixed size allocated by the first quadform call (in no byte count)
     double* d_qf = nullptr;
     double last_half_ms = 0, last_quadform_ms = 0, last_sample_ms = 0;
+    // sf_chol_plan_gram / _gram_device (sf_gram.hip): the Y store -- gram_chunks row-major n x SVM_W blocks, the parts of one chunk
+    // row, the result block of the host-array call -- allocated or grown by the first call that needs it (bytes_gram, not in
+    // bytes_device); last_gram_parts: slabs per tile of the last call (0: the one-column path)
+    double* d_gram = nullptr;
+    int64_t gram_chunks = 0;
+    size_t bytes_gram = 0;
+    double last_gram_ms = 0;
+    int last_gram_parts = 0;
     // sf_*_plan_set_ordering / _set_value_map (sf_device_io.hip): perm[new] = old as 32-bit indices (as d_Lsi), the value map
     // (nnz entries for Lx, then unz for Ux) and the parts of the LU plans' max |a_ij|; bytes_ordering is not in bytes_device
     int32_t* d_perm = nullptr;

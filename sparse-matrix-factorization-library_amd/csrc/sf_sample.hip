@@ -229,6 +229,8 @@ void half_add_ms(sf_chol_plan* p, double* total) {
 
 }  // namespace
 
+int sf_quadform_scratch(sf_chol_plan* p) { return half_qf_scratch(p); }
+
 extern "C" {
 
 int sf_chol_plan_solve_half(sf_chol_plan* p, int which, sf_long nrhs, const sf_float* B, sf_long ldb, sf_float* X, sf_long ldx) {
