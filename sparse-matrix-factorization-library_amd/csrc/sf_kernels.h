@@ -255,6 +255,41 @@ constexpr int SEL_SMALL_M = 512;      // rows below <= SEL_SMALL_M,
 constexpr int SEL_SMALL_Y = 4096;     // (rows below) x nscol <= SEL_SMALL_Y
 constexpr int SEL_MAX_SLABS = 16;     // K slabs of the split products
 
+// the structure arrays Sigma(R,R) is addressed through (device pointers).  Xp: the panels' offsets in the arena and in the factor
+// (Lsxp of a Cholesky plan, Xp of an LU plan); pairs / relmap: the scatter problems' table and relative maps
+struct SelStruct {
+    const int32_t *Super, *SuperMap;
+    const int64_t* Lsip;
+    const int32_t* Lsi;
+    const int64_t* Xp;
+    const SelPair* pairs;
+    const int32_t* relmap;
+};
+// one launch each, on the kernels of sf_selinv.hip / sf_selinv_lu.hip; the plans' entry points run these and nothing else
+void launch_selinv_small(const SelUnit* units, int nunits, const double* Lsx, double* S, const SelStruct& t, hipStream_t st);
+void launch_selinv_trinv(const SelUnit& u, const double* Lsx, double* Linv, hipStream_t st);
+// C (M x N, ldc) = op(A) B (+ C when acc_in), am = 0: A plain, 1: A = X^T, 2: A = Sigma(R,R) of unit u gathered from (S, S2); K cut
+// into `slabs` slabs of kslab = the share of a slab rounded up to 16, slab z written to C + z cstride (a slab past K: zeros)
+void launch_selinv_gemm(int am, int M, int N, int K, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
+                        int slabs, int64_t cstride, int acc_in, const SelUnit& u, const double* S, const double* S2, const SelStruct& t,
+                        hipStream_t st);
+// dst[e] (+)= sum_{z < nslab} src[z * stride + e], e < count, z in increasing order
+void launch_selinv_sum(const double* src, int nslab, int64_t stride, int64_t count, double* dst, int acc_in, hipStream_t st);
+void launch_selinv_finish(const SelUnit& u, const double* Z, const double* Sc, double* S, hipStream_t st);
+void launch_selinv_diag(int64_t n, const double* S, const SelStruct& t, double* d, hipStream_t st);
+// buf: ceil(n / 256) partial sums, then the result 2 sum log L_jj
+void launch_logdet(int64_t n, const double* Lsx, const SelStruct& t, double* buf, hipStream_t st);
+void launch_lu_selinv_small(const SelUnit* units, int nunits, const double* PL, const double* PU, double* SL, double* SU, const SelStruct& t,
+                            hipStream_t st);
+void launch_lu_selinv_trinv(const SelUnit& u, const double* P, int unit, double* Tinv, hipStream_t st);
+void launch_lu_selinv_finish(const SelUnit& u, const double* Zl, const double* Zu, const double* Sc, double* SL, double* SU, hipStream_t st);
+// RefXp: the packed panels' offsets (nsuper + 1)
+void launch_lu_selinv_pack(const SelStruct& t, const int64_t* RefXp, int32_t nsuper, const double* SL, const double* SU, double* out,
+                           int64_t e_begin, int64_t e_end, hipStream_t st);
+void launch_lu_selinv_diag(int64_t n, const double* SL, const SelStruct& t, double* d, hipStream_t st);
+// buf: ceil(n / 256) partial sums, then sum log|U_jj| and the parity of the negative U_jj (as a double); neg: ceil(n / 256) counts
+void launch_lu_logdet(int64_t n, const double* PU, const SelStruct& t, double* buf, int32_t* neg, hipStream_t st);
+
 void launch_noop(hipStream_t st);
 
 // ---- residual and iterative refinement (sf_refine.hip, sf_chol_plan_residual / sf_chol_plan_refine) ----

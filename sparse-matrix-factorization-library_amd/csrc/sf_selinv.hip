@@ -197,6 +197,48 @@ k_logdet_final(const double* __restrict__ part, int64_t np, double* __restrict__
     if (threadIdx.x == 0) out[0] = 2.0 * red[0];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// the launchers (sf_kernels.h): one launch each
+// ---------------------------------------------------------------------------------------------------------------------------
+void launch_selinv_small(const SelUnit* units, int nunits, const double* Lsx, double* S, const SelStruct& t, hipStream_t st) {
+    if (nunits <= 0) return;
+    hipLaunchKernelGGL(k_selinv_small, dim3((unsigned)nunits), dim3(256), 0, st, units, Lsx, S, t.Super, t.SuperMap, t.Lsip, t.Lsi, t.Xp,
+                       t.pairs, t.relmap);
+}
+
+void launch_selinv_trinv(const SelUnit& u, const double* Lsx, double* Linv, hipStream_t st) {
+    hipLaunchKernelGGL(k_selinv_trinv, dim3(u.w), dim3(SEL_UW), 0, st, u, Lsx, Linv);
+}
+
+void launch_selinv_gemm(int am, int M, int N, int K, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
+                        int slabs, int64_t cstride, int acc_in, const SelUnit& u, const double* S, const double* S2, const SelStruct& t,
+                        hipStream_t st) {
+    if (am == 0) selinv_gemm<0>(M, N, K, A, lda, B, ldb, C, ldc, slabs, cstride, acc_in, u, S, S2, t, st);
+    else if (am == 1) selinv_gemm<1>(M, N, K, A, lda, B, ldb, C, ldc, slabs, cstride, acc_in, u, S, S2, t, st);
+    else selinv_gemm<2>(M, N, K, A, lda, B, ldb, C, ldc, slabs, cstride, acc_in, u, S, S2, t, st);
+}
+
+void launch_selinv_sum(const double* src, int nslab, int64_t stride, int64_t count, double* dst, int acc_in, hipStream_t st) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_selinv_sum, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, src, nslab, stride, count, dst, acc_in);
+}
+
+void launch_selinv_finish(const SelUnit& u, const double* Z, const double* Sc, double* S, hipStream_t st) {
+    const int64_t w = u.w, m = u.nsrow - u.cb - u.w;
+    const int64_t tot = m * w + w * w;
+    hipLaunchKernelGGL(k_selinv_finish, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, u, Z, Sc, S);
+}
+
+void launch_selinv_diag(int64_t n, const double* S, const SelStruct& t, double* d, hipStream_t st) {
+    hipLaunchKernelGGL(k_selinv_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, S, t.Super, t.SuperMap, t.Lsip, t.Xp, d);
+}
+
+void launch_logdet(int64_t n, const double* Lsx, const SelStruct& t, double* buf, hipStream_t st) {
+    const int64_t nb = (n + 255) / 256;
+    hipLaunchKernelGGL(k_logdet_part, dim3((unsigned)nb), dim3(256), 0, st, n, Lsx, t.Super, t.SuperMap, t.Lsip, t.Xp, buf);
+    hipLaunchKernelGGL(k_logdet_final, dim3(1), dim3(256), 0, st, (const double*)buf, nb, buf + nb);
+}
+
 }  // namespace sf
 
 // ===========================================================================================================================
@@ -295,11 +337,6 @@ int sf_selinv_schedule(sf_chol_plan* p) {
     return SF_OK;
 }
 
-void sf_selinv_slab_sum(const double* src, int nslab, int64_t count, double* dst, int acc_in, hipStream_t st) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL(sf::k_selinv_sum, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, src, nslab, count, count, dst, acc_in);
-}
-
 namespace {
 
 // arena + scratch; on failure everything allocated here is released and the plan is as before
@@ -334,7 +371,7 @@ int selinv_alloc(sf_chol_plan* p) {
 template <int AM>
 void gemm(sf_chol_plan* p, int M, int N, int K, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
           int slabs, int64_t cstride, int acc_in, const SelUnit& u, hipStream_t st) {
-    sf::selinv_gemm<AM>(p, M, N, K, A, lda, B, ldb, C, ldc, slabs, cstride, acc_in, u, sf::SelArenas{p->d_sel, p->d_sel, p->d_Lsxp}, st);
+    sf::selinv_gemm<AM>(M, N, K, A, lda, B, ldb, C, ldc, slabs, cstride, acc_in, u, p->d_sel, p->d_sel, sf::sel_struct(p), st);
 }
 
 // one unit of a wide or long supernode
@@ -348,7 +385,7 @@ void run_big(sf_chol_plan* p, const sf_chol_plan::SelBig& b, hipStream_t st) {
     double* Ssl = Zsl + p->sel_z_elems;
     double* Sc = Ssl + p->sel_s_elems;
     const double* L = p->d_Lsx;
-    hipLaunchKernelGGL(sf::k_selinv_trinv, dim3(w), dim3(sf::SEL_UW), 0, st, u, L, Linv);
+    sf::launch_selinv_trinv(u, L, Linv, st);
     // Sc = Linv^T Linv
     gemm<1>(p, w, w, w, Linv, w, Linv, w, Sc, w, 1, 0, 0, u, st);
     if (m > 0) {
@@ -357,18 +394,16 @@ void run_big(sf_chol_plan* p, const sf_chol_plan::SelBig& b, hipStream_t st) {
             gemm<2>(p, m, w, m, nullptr, 0, Y, m, Zs, m, 1, 0, 0, u, st);                                               // Z = Sigma(R,R) Y
         } else {
             gemm<2>(p, m, w, m, nullptr, 0, Y, m, Zsl, m, b.zslabs, (int64_t)m * w, 0, u, st);
-            sf_selinv_slab_sum(Zsl, b.zslabs, (int64_t)m * w, Zs, 0, st);
+            sf::launch_selinv_sum(Zsl, b.zslabs, (int64_t)m * w, (int64_t)m * w, Zs, 0, st);
         }
         if (b.sslabs == 1) {
             gemm<1>(p, w, w, m, Y, m, Zs, m, Sc, w, 1, 0, 1, u, st);                                                      // Sc += Y^T Z
         } else {
             gemm<1>(p, w, w, m, Y, m, Zs, m, Ssl, w, b.sslabs, (int64_t)w * w, 0, u, st);
-            sf_selinv_slab_sum(Ssl, b.sslabs, (int64_t)w * w, Sc, 1, st);
+            sf::launch_selinv_sum(Ssl, b.sslabs, (int64_t)w * w, (int64_t)w * w, Sc, 1, st);
         }
     }
-    const int64_t tot = (int64_t)m * w + (int64_t)w * w;
-    hipLaunchKernelGGL(sf::k_selinv_finish, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, u, (const double*)Zs, (const double*)Sc,
-                       p->d_sel);
+    sf::launch_selinv_finish(u, Zs, Sc, p->d_sel, st);
 }
 
 }  // namespace
@@ -393,10 +428,7 @@ int sf_chol_plan_selinv(sf_chol_plan* p) {
     HIP_TRY(hipEventRecord(p->ev_s0, st));
     for (const auto& s : p->sel_steps) {
         for (int64_t k = s.big_first; k < s.big_first + s.big_count; ++k) run_big(p, p->sel_big[k], st);
-        if (s.small_count > 0)
-            hipLaunchKernelGGL(sf::k_selinv_small, dim3((unsigned)s.small_count), dim3(256), 0, st,
-                               (const SelUnit*)p->d_sel_units + s.small_first, (const double*)p->d_Lsx, p->d_sel, p->d_Super, p->d_SuperMap,
-                               p->d_Lsip, p->d_Lsi, p->d_Lsxp, (const sf::SelPair*)p->d_sel_pairs, p->d_relmap);
+        sf::launch_selinv_small((const SelUnit*)p->d_sel_units + s.small_first, (int)s.small_count, p->d_Lsx, p->d_sel, sf::sel_struct(p), st);
     }
     HIP_TRY(hipEventRecord(p->ev_s1, st));
     HIP_TRY(hipGetLastError());
@@ -423,8 +455,7 @@ int sf_chol_plan_selinv_diag(sf_chol_plan* p, sf_float* d) {
     if (p->n <= 0) return SF_OK;
     if (!p->d_sel || p->sel_gen != p->factor_gen) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
-    hipLaunchKernelGGL(sf::k_selinv_diag, dim3((unsigned)((p->n + 255) / 256)), dim3(256), 0, p->stream, (int64_t)p->n, (const double*)p->d_sel,
-                       p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsxp, p->d_sel_diag);
+    sf::launch_selinv_diag((int64_t)p->n, p->d_sel, sf::sel_struct(p), p->d_sel_diag, p->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(d, p->d_sel_diag, (size_t)p->n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
@@ -440,9 +471,7 @@ int sf_chol_plan_logdet(sf_chol_plan* p, sf_float* out) {
     const int64_t nb = (p->n + 255) / 256;
     double* buf = nullptr;
     HIP_TRY(hipMalloc((void**)&buf, (size_t)(nb + 1) * sizeof(double)));
-    hipLaunchKernelGGL(sf::k_logdet_part, dim3((unsigned)nb), dim3(256), 0, p->stream, (int64_t)p->n, (const double*)p->d_Lsx, p->d_Super,
-                       p->d_SuperMap, p->d_Lsip, p->d_Lsxp, buf);
-    hipLaunchKernelGGL(sf::k_logdet_final, dim3(1), dim3(256), 0, p->stream, (const double*)buf, nb, buf + nb);
+    sf::launch_logdet((int64_t)p->n, p->d_Lsx, sf::sel_struct(p), buf, p->stream);
     const hipError_t e1 = hipGetLastError();
     const hipError_t e2 = hipMemcpyAsync(out, buf + nb, sizeof(double), hipMemcpyDeviceToHost, p->stream);
     const hipError_t e3 = hipStreamSynchronize(p->stream);

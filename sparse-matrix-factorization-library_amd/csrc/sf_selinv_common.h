@@ -136,17 +136,22 @@ k_selinv_gemm(int M, int N, int K, const double* __restrict__ A, int64_t lda, co
             }
 }
 
-// the gathered operand's arenas and the panels' offsets in them (AM == 2 only)
-struct SelArenas { const double *S, *S2; const int64_t* Xp; };
-
+// the one place a product is launched from: launch_selinv_gemm (sf_selinv.hip) is a switch over these three, and the wide units of
+// both plans call them directly (S, S2: the gathered operand's arenas, AM == 2 only)
 template <int AM>
-static inline void selinv_gemm(sf_chol_plan* p, int M, int N, int K, const double* A, int64_t lda, const double* B, int64_t ldb, double* C,
-                               int64_t ldc, int slabs, int64_t cstride, int acc_in, const SelUnit& u, const SelArenas& ar, hipStream_t st) {
+static inline void selinv_gemm(int M, int N, int K, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
+                               int slabs, int64_t cstride, int acc_in, const SelUnit& u, const double* S, const double* S2, const SelStruct& t,
+                               hipStream_t st) {
     if (M <= 0 || N <= 0) return;
     const int kslab = ((K + slabs - 1) / slabs + SG_K - 1) / SG_K * SG_K;
     const dim3 grid((M + 63) / 64, (N + 63) / 64, slabs);
-    hipLaunchKernelGGL(k_selinv_gemm<AM>, grid, dim3(256), 0, st, M, N, K, A, lda, B, ldb, C, ldc, kslab, cstride, acc_in, u, ar.S, ar.S2,
-                       p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, ar.Xp, (const SelPair*)p->d_sel_pairs, p->d_relmap);
+    hipLaunchKernelGGL(k_selinv_gemm<AM>, grid, dim3(256), 0, st, M, N, K, A, lda, B, ldb, C, ldc, kslab, cstride, acc_in, u, S, S2,
+                       t.Super, t.SuperMap, t.Lsip, t.Lsi, t.Xp, t.pairs, t.relmap);
+}
+
+// the plan's structure arrays as the launchers take them
+static inline SelStruct sel_struct(const sf_chol_plan* p) {
+    return SelStruct{p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, p->lu ? p->d_Xp : p->d_Lsxp, (const SelPair*)p->d_sel_pairs, p->d_relmap};
 }
 
 }  // namespace sf
@@ -156,5 +161,3 @@ static inline void selinv_gemm(sf_chol_plan* p, int M, int N, int K, const doubl
 bool sf_selinv_factor_current(sf_chol_plan* p);
 // the schedule (first call): units, pair table, scratch sizes, flops_selinv (an LU unit costs twice a Cholesky one)
 int sf_selinv_schedule(sf_chol_plan* p);
-// dst[e] (+)= sum_{z < nslab} src[z * count + e], z in increasing order
-void sf_selinv_slab_sum(const double* src, int nslab, int64_t count, double* dst, int acc_in, hipStream_t st);

@@ -250,6 +250,44 @@ k_lu_logdet_final(const double* __restrict__ part, const int32_t* __restrict__ n
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// the launchers (sf_kernels.h): one launch each
+// ---------------------------------------------------------------------------------------------------------------------------
+void launch_lu_selinv_small(const SelUnit* units, int nunits, const double* PL, const double* PU, double* SL, double* SU, const SelStruct& t,
+                            hipStream_t st) {
+    if (nunits <= 0) return;
+    hipLaunchKernelGGL(k_lu_selinv_small, dim3((unsigned)nunits), dim3(256), 0, st, units, PL, PU, SL, SU, t.Super, t.SuperMap, t.Lsip, t.Lsi,
+                       t.Xp, t.pairs, t.relmap);
+}
+
+void launch_lu_selinv_trinv(const SelUnit& u, const double* P, int unit, double* Tinv, hipStream_t st) {
+    hipLaunchKernelGGL(k_lu_selinv_trinv, dim3(u.w), dim3(SEL_UW), 0, st, u, P, unit, Tinv);
+}
+
+void launch_lu_selinv_finish(const SelUnit& u, const double* Zl, const double* Zu, const double* Sc, double* SL, double* SU, hipStream_t st) {
+    const int64_t w = u.w, m = u.nsrow - u.cb - u.w;
+    const int64_t tot = m * w + w * w;
+    hipLaunchKernelGGL(k_lu_selinv_finish, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, u, Zl, Zu, Sc, SL, SU);
+}
+
+void launch_lu_selinv_pack(const SelStruct& t, const int64_t* RefXp, int32_t nsuper, const double* SL, const double* SU, double* out,
+                           int64_t e_begin, int64_t e_end, hipStream_t st) {
+    const int64_t blocks = (e_end - e_begin + 255) / 256;
+    if (blocks <= 0) return;
+    hipLaunchKernelGGL(k_lu_selinv_pack, dim3((unsigned)std::min<int64_t>(blocks, 65536)), dim3(256), 0, st, t.Super, t.Lsip, t.Xp, RefXp, nsuper,
+                       SL, SU, out, e_begin, e_end);
+}
+
+void launch_lu_selinv_diag(int64_t n, const double* SL, const SelStruct& t, double* d, hipStream_t st) {
+    hipLaunchKernelGGL(k_lu_selinv_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, SL, t.Super, t.SuperMap, t.Lsip, t.Xp, d);
+}
+
+void launch_lu_logdet(int64_t n, const double* PU, const SelStruct& t, double* buf, int32_t* neg, hipStream_t st) {
+    const int64_t nb = (n + 255) / 256;
+    hipLaunchKernelGGL(k_lu_logdet_part, dim3((unsigned)nb), dim3(256), 0, st, n, PU, t.Super, t.SuperMap, t.Lsip, t.Xp, buf, neg);
+    hipLaunchKernelGGL(k_lu_logdet_final, dim3(1), dim3(256), 0, st, (const double*)buf, (const int32_t*)neg, nb, buf + nb);
+}
+
 }  // namespace sf
 
 // ===========================================================================================================================
@@ -316,12 +354,12 @@ void gathered_product(sf_chol_plan* p, const sf_chol_plan::SelBig& b, const doub
                       double* Zsl, hipStream_t st) {
     const SelUnit& u = b.u;
     const int w = u.w, m = u.nsrow - u.cb - u.w;
-    const sf::SelArenas ar{S, S2, p->d_Xp};
+    const sf::SelStruct t = sf::sel_struct(p);
     if (b.zslabs == 1) {
-        sf::selinv_gemm<2>(p, m, w, m, nullptr, 0, Y, m, Z, m, 1, 0, 0, u, ar, st);
+        sf::selinv_gemm<2>(m, w, m, nullptr, 0, Y, m, Z, m, 1, 0, 0, u, S, S2, t, st);
     } else {
-        sf::selinv_gemm<2>(p, m, w, m, nullptr, 0, Y, m, Zsl, m, b.zslabs, (int64_t)m * w, 0, u, ar, st);
-        sf_selinv_slab_sum(Zsl, b.zslabs, (int64_t)m * w, Z, 0, st);
+        sf::selinv_gemm<2>(m, w, m, nullptr, 0, Y, m, Zsl, m, b.zslabs, (int64_t)m * w, 0, u, S, S2, t, st);
+        sf::launch_selinv_sum(Zsl, b.zslabs, (int64_t)m * w, (int64_t)m * w, Z, 0, st);
     }
 }
 
@@ -334,27 +372,26 @@ void run_big(sf_chol_plan* p, const sf_chol_plan::SelBig& b, hipStream_t st) {
     const double* PU = p->d_Lsx + p->xC;
     double* SL = p->d_sel;
     double* SU = p->d_sel + p->xC;
-    const sf::SelArenas none{nullptr, nullptr, p->d_Xp};
-    hipLaunchKernelGGL(sf::k_lu_selinv_trinv, dim3(w), dim3(sf::SEL_UW), 0, st, u, PL, 1, s.Tl);
-    hipLaunchKernelGGL(sf::k_lu_selinv_trinv, dim3(w), dim3(sf::SEL_UW), 0, st, u, PU, 0, s.Tu);
+    const sf::SelStruct t = sf::sel_struct(p);
+    const double* none = nullptr;       // the plain and transposed products gather nothing
+    sf::launch_lu_selinv_trinv(u, PL, 1, s.Tl, st);
+    sf::launch_lu_selinv_trinv(u, PU, 0, s.Tu, st);
     // Sc = Tu^-T Tl^-1
-    sf::selinv_gemm<1>(p, w, w, w, s.Tu, w, s.Tl, w, s.Sc, w, 1, 0, 0, u, none, st);
+    sf::selinv_gemm<1>(w, w, w, s.Tu, w, s.Tl, w, s.Sc, w, 1, 0, 0, u, none, none, t, st);
     if (m > 0) {
         const int64_t below = u.lx + (int64_t)u.cb * u.nsrow + u.cb + w;        // P(R,C) in its panel set
-        sf::selinv_gemm<0>(p, m, w, w, PL + below, u.nsrow, s.Tl, w, s.Yl, m, 1, 0, 0, u, none, st);      // Yl = PL(R,C) Tl^-1
-        sf::selinv_gemm<0>(p, m, w, w, PU + below, u.nsrow, s.Tu, w, s.Yu, m, 1, 0, 0, u, none, st);      // Yu = PU(R,C) Tu^-1
+        sf::selinv_gemm<0>(m, w, w, PL + below, u.nsrow, s.Tl, w, s.Yl, m, 1, 0, 0, u, none, none, t, st);      // Yl = PL(R,C) Tl^-1
+        sf::selinv_gemm<0>(m, w, w, PU + below, u.nsrow, s.Tu, w, s.Yu, m, 1, 0, 0, u, none, none, t, st);      // Yu = PU(R,C) Tu^-1
         gathered_product(p, b, SL, SU, s.Yl, s.Zl, s.Zsl, st);                                            // Zl = G Yl
         gathered_product(p, b, SU, SL, s.Yu, s.Zu, s.Zsl, st);                                            // Zu = G^T Yu
         if (b.sslabs == 1) {
-            sf::selinv_gemm<1>(p, w, w, m, s.Yu, m, s.Zl, m, s.Sc, w, 1, 0, 1, u, none, st);              // Sc += Yu^T Zl
+            sf::selinv_gemm<1>(w, w, m, s.Yu, m, s.Zl, m, s.Sc, w, 1, 0, 1, u, none, none, t, st);              // Sc += Yu^T Zl
         } else {
-            sf::selinv_gemm<1>(p, w, w, m, s.Yu, m, s.Zl, m, s.Ssl, w, b.sslabs, (int64_t)w * w, 0, u, none, st);
-            sf_selinv_slab_sum(s.Ssl, b.sslabs, (int64_t)w * w, s.Sc, 1, st);
+            sf::selinv_gemm<1>(w, w, m, s.Yu, m, s.Zl, m, s.Ssl, w, b.sslabs, (int64_t)w * w, 0, u, none, none, t, st);
+            sf::launch_selinv_sum(s.Ssl, b.sslabs, (int64_t)w * w, (int64_t)w * w, s.Sc, 1, st);
         }
     }
-    const int64_t tot = (int64_t)m * w + (int64_t)w * w;
-    hipLaunchKernelGGL(sf::k_lu_selinv_finish, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, u, (const double*)s.Zl,
-                       (const double*)s.Zu, (const double*)s.Sc, SL, SU);
+    sf::launch_lu_selinv_finish(u, s.Zl, s.Zu, s.Sc, SL, SU, st);
 }
 
 // +1 / -1: the parity of the permutation pivpos (n - number of cycles)
@@ -392,11 +429,8 @@ int sf_lu_plan_selinv(sf_lu_plan* p) {
     HIP_TRY(hipEventRecord(p->ev_s0, st));
     for (const auto& s : p->sel_steps) {
         for (int64_t k = s.big_first; k < s.big_first + s.big_count; ++k) run_big(p, p->sel_big[k], st);
-        if (s.small_count > 0)
-            hipLaunchKernelGGL(sf::k_lu_selinv_small, dim3((unsigned)s.small_count), dim3(256), 0, st,
-                               (const SelUnit*)p->d_sel_units + s.small_first, (const double*)p->d_Lsx, (const double*)(p->d_Lsx + p->xC),
-                               p->d_sel, p->d_sel + p->xC, p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, p->d_Xp,
-                               (const sf::SelPair*)p->d_sel_pairs, p->d_relmap);
+        sf::launch_lu_selinv_small((const SelUnit*)p->d_sel_units + s.small_first, (int)s.small_count, p->d_Lsx, p->d_Lsx + p->xC, p->d_sel,
+                                   p->d_sel + p->xC, sf::sel_struct(p), st);
     }
     HIP_TRY(hipEventRecord(p->ev_s1, st));
     HIP_TRY(hipGetLastError());
@@ -418,10 +452,8 @@ int sf_lu_plan_get_selinv_range(sf_lu_plan* p, sf_long e_begin, sf_long e_end, s
         (void)hipGetLastError();
         return SF_ERR_ALLOC;
     }
-    const int64_t blocks = (count + 255) / 256;
-    hipLaunchKernelGGL(sf::k_lu_selinv_pack, dim3((unsigned)std::min<int64_t>(blocks, 65536)), dim3(256), 0, p->stream, p->d_Super, p->d_Lsip,
-                       p->d_Xp, p->d_Lsxp, (int32_t)p->nsuper, (const double*)p->d_sel, (const double*)(p->d_sel + p->xC), tmp,
-                       (int64_t)e_begin, (int64_t)e_end);
+    sf::launch_lu_selinv_pack(sf::sel_struct(p), p->d_Lsxp, (int32_t)p->nsuper, p->d_sel, p->d_sel + p->xC, tmp, (int64_t)e_begin,
+                              (int64_t)e_end, p->stream);
     const hipError_t e1 = hipGetLastError();
     const hipError_t e2 = hipMemcpyAsync(out, tmp, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, p->stream);
     const hipError_t e3 = hipStreamSynchronize(p->stream);
@@ -434,8 +466,7 @@ int sf_lu_plan_selinv_diag(sf_lu_plan* p, sf_float* d) {
     if (p->n <= 0) return SF_OK;
     if (!p->d_sel || p->sel_gen != p->factor_gen) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
-    hipLaunchKernelGGL(sf::k_lu_selinv_diag, dim3((unsigned)((p->n + 255) / 256)), dim3(256), 0, p->stream, (int64_t)p->n,
-                       (const double*)p->d_sel, p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Xp, p->d_sel_diag);
+    sf::launch_lu_selinv_diag((int64_t)p->n, p->d_sel, sf::sel_struct(p), p->d_sel_diag, p->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(d, p->d_sel_diag, (size_t)p->n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
@@ -455,9 +486,7 @@ int sf_lu_plan_logdet(sf_lu_plan* p, sf_float* logabs, int* sign) {
     HIP_TRY(hipMalloc((void**)&buf, (size_t)(nb + 2) * sizeof(double) + (size_t)nb * sizeof(int32_t)));
     int32_t* neg = (int32_t*)(buf + nb + 2);
     double res[2] = {0.0, 0.0};
-    hipLaunchKernelGGL(sf::k_lu_logdet_part, dim3((unsigned)nb), dim3(256), 0, p->stream, (int64_t)p->n, (const double*)(p->d_Lsx + p->xC),
-                       p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Xp, buf, neg);
-    hipLaunchKernelGGL(sf::k_lu_logdet_final, dim3(1), dim3(256), 0, p->stream, (const double*)buf, (const int32_t*)neg, nb, buf + nb);
+    sf::launch_lu_logdet((int64_t)p->n, p->d_Lsx + p->xC, sf::sel_struct(p), buf, neg, p->stream);
     const hipError_t e1 = hipGetLastError();
     const hipError_t e2 = hipMemcpyAsync(res, buf + nb, 2 * sizeof(double), hipMemcpyDeviceToHost, p->stream);
     const hipError_t e3 = hipStreamSynchronize(p->stream);

@@ -9,6 +9,10 @@ rounding is far below the bounds.  Every bound is per ELEMENT, of the form the a
     TRSM           |X^ D^T - B|   <= SAFETY (b + 2) u |X^| |D^T|
     LU panel       |A - L~ U~|    <= SAFETY (terms + 2) u |L~| |U~|      (fused steps, from the stored factor: lu_panel_check)
     solve sweeps   |sum of an equation's terms - its right-hand side| <= SAFETY (terms) u (sum of the terms' magnitudes)
+    selinv GEMM    |C^ - C|       <= SAFETY (K_z + 2) u (|C0| + |op(A)| |B|)   per K slab z (K_z = its K range; an empty slab: +0.0)
+    selinv trinv   |T X^ - I|     <= SAFETY (w + 2) u |T| |X^|                 (unit or stored diagonal; strict upper part +0.0)
+    selinv small   forward bound through T^-1 -> Y -> Z -> Sigma(C,C) with absolute-value matrices (small_ref)
+    selinv sum / finish / diag / pack: bit for bit;  logdet: SAFETY (8 + ceil(np / 256) + 2) u sum|log| + u sum|log|
 A max-normalised metric (max error / max |ref|) would hide an error in a row scaled by 1e-6; these do not.
 
 Arena: the tests place every operand in one fp64 host image (the probe copies it to the device, launches once and copies
@@ -339,3 +343,208 @@ def lu_panel_check(A11, A21, A12, PL, PU, pos, perturbed, J, what):
         raise AssertionError(f"{what}: {int(viol.sum())} elements of |A - L U| beyond the bound, first at row {k[0] + J} column {k[1] + J} "
                              f"(err {float(err[k]):.3e}, bound {float(bound[k]):.3e})")
     return float(np.max(np.where(check, err / np.maximum(bound, np.finfo(LD).tiny), 0)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the selected inversion, one launch at a time (csrc/sf_selinv.hip, sf_selinv_lu.hip): tests/test_kernels_selinv.py
+# ---------------------------------------------------------------------------------------------------------------------
+SG_K = 16                    # K chunk of k_selinv_gemm
+SEL_FAULTS = ("swap arenas", "wrong pair", "dropped chunk", "slab overlap", "stored diagonal", "mirror outside J")
+
+
+def within_ratio(got, ref, bound, what):
+    """assert_within, returning the worst err / bound (0 / 0 counts as 0)"""
+    assert_within(got, ref, bound, what)
+    err = np.abs(np.asarray(got).astype(LD) - ref)
+    return float(np.max(np.where(err > 0, err / np.maximum(bound, np.finfo(LD).tiny), 0), initial=0.0))
+
+
+class SelTables:
+    """The pair table and the relative maps of a supernodal structure as sf_selinv_schedule and k_build_relmaps lay them out: for
+    every supernode J and every ancestor a that J's rows below fall into, in row order, one pair (i, map_off) -- i = the panel
+    position of J's first row in a, relmap[map_off + k] = the position of J's panel row i + k in the row list of a, for ALL rows
+    from i to the end of J's list.  Written with a dictionary lookup, not with the searchsorted of selinv_ref.py."""
+
+    def __init__(self, Super, Lsip, Lsi, Xp, pad=0):
+        self.Super, self.Lsip, self.Lsi, self.Xp = (np.asarray(v) for v in (Super, Lsip, Lsi, Xp))
+        self.nsuper = len(self.Super) - 1
+        self.n = int(self.Super[-1])
+        self.SuperMap = np.repeat(np.arange(self.nsuper), np.diff(self.Super)).astype(np.int32)
+        self.pairs, self.pair0, relmap = [], [0], [np.full(pad, -(1 << 30), dtype=np.int64)]
+        off = pad
+        for s in range(self.nsuper):
+            ncol, rows = self.ncol(s), self.rows(s)
+            i = ncol
+            while i < len(rows):
+                a = self.SuperMap[rows[i]]
+                where = {int(g): k for k, g in enumerate(self.rows(a))}
+                self.pairs.append((off, i))
+                relmap.append(np.array([where[int(g)] for g in rows[i:]], dtype=np.int64))
+                off += len(rows) - i
+                while i < len(rows) and self.SuperMap[rows[i]] == a:
+                    i += 1
+            self.pair0.append(len(self.pairs))
+        self.relmap = np.concatenate(relmap)
+
+    def ncol(self, s):
+        return int(self.Super[s + 1] - self.Super[s])
+
+    def nsrow(self, s):
+        return int(self.Lsip[s + 1] - self.Lsip[s])
+
+    def rows(self, s):
+        return self.Lsi[self.Lsip[s]:self.Lsip[s + 1]]
+
+    def gather_index(self, J, ce, fault=None):
+        """idx (m x m): entry (x, y) of Sigma(R,R) of the unit of J whose R starts at panel position ce lies at arena index
+        idx[x, y]: in column min(x, y)'s panel at the row position of max(x, y) (sel_col / sel_at).  fault "wrong pair": a column
+        of J's second or later pair is addressed with the pair before it."""
+        ns, nc = self.nsrow(J), self.ncol(J)
+        m = ns - ce
+        idx = np.zeros((m, m), dtype=np.int64)
+        prs = self.pairs[self.pair0[J]:self.pair0[J + 1]]
+        for y in range(m):
+            q = ce + y
+            hi = np.arange(q, ns)
+            if q < nc:
+                at = self.Xp[J] + q * ns + hi
+            else:
+                k = max(t for t, pr in enumerate(prs) if pr[1] <= q)
+                if fault == "wrong pair" and k > 0:
+                    k -= 1
+                g = self.Lsi[self.Lsip[J] + q]
+                a = self.SuperMap[g]
+                at = self.Xp[a] + (g - self.Super[a]) * self.nsrow(a) + self.relmap[prs[k][0] - prs[k][1] + hi]
+            idx[y:, y] = at
+            idx[y, y:] = at
+        return idx
+
+    def gather(self, J, ce, S, S2, fault=None):
+        """Sigma(R,R): on and below the diagonal from S, above it from S2 ("swap arenas": the other way round)"""
+        idx = self.gather_index(J, ce, fault)
+        if fault == "swap arenas":
+            S, S2 = S2, S
+        low = np.tril(np.ones(idx.shape, dtype=bool))
+        return np.where(low, S[idx], S2[idx]), idx
+
+
+def sel_slabs(K, slabs, fault=None):
+    """[k0, k1) of every slab as selinv_gemm cuts K: kslab = the share of a slab rounded up to a multiple of the 16-deep chunk.
+    Faults: the last partial chunk of a slab dropped; every slab but the last running one chunk into the next."""
+    kslab = ((K + slabs - 1) // slabs + SG_K - 1) // SG_K * SG_K
+    out = []
+    for z in range(slabs):
+        k0 = min(K, z * kslab)
+        k1 = min(K, k0 + kslab)
+        if fault == "dropped chunk":
+            k1 -= (k1 - k0) % SG_K
+        if fault == "slab overlap" and z < slabs - 1:
+            k1 = min(K, k1 + SG_K)
+        out.append((k0, k1))
+    return out
+
+
+def selgemm_emulate(opA, B, C0, slabs, acc_in, fault=None):
+    """float64 emulation of one k_selinv_gemm launch: slab z = op(A)[:, k0:k1] B[k0:k1] (+ its own prior content when acc_in).
+    C0: slabs x M x N.  Returns slabs x M x N."""
+    out = np.zeros(C0.shape)
+    for z, (k0, k1) in enumerate(sel_slabs(opA.shape[1], slabs, fault)):
+        out[z] = opA[:, k0:k1] @ B[k0:k1]
+        if acc_in:
+            out[z] = C0[z] + out[z]
+    return out
+
+
+def selgemm_check(got, opA, B, C0, slabs, acc_in, what):
+    """every slab against the longdouble product over its own K range; returns the worst err / bound"""
+    worst = 0.0
+    for z, (k0, k1) in enumerate(sel_slabs(opA.shape[1], slabs)):
+        prior = np.abs(np.asarray(C0[z], dtype=LD)) if acc_in else 0
+        ref = matmul_ld(opA[:, k0:k1], B[k0:k1]) + (np.asarray(C0[z], dtype=LD) if acc_in else 0)
+        bound = SAFETY * (k1 - k0 + 2) * U * (prior + matmul_ld(np.abs(opA[:, k0:k1]), np.abs(B[k0:k1])))
+        if k1 == k0 and not acc_in and np.any(bits(got[z]) != 0):
+            raise AssertionError(f"{what}: slab {z} has no K range and is beyond the bound: it does not hold +0.0 throughout")
+        worst = max(worst, within_ratio(got[z], ref, bound, f"{what} slab {z} K [{k0}, {k1})"))
+    return worst
+
+
+def tri_lower(T, unit):
+    """the triangle a trinv launch reads: the strict lower part of T with an implied unit diagonal, or with the stored one"""
+    return np.tril(T, -1) + (np.eye(T.shape[0]) if unit else np.diag(np.diag(T)))
+
+
+def trinv_emulate(T, unit, fault=None, dtype=np.float64):
+    """column-oriented forward substitution T X = I as the kernels do it (all columns at once); "stored diagonal": unit ignored"""
+    w = T.shape[0]
+    T = np.asarray(T, dtype=dtype)
+    Bm = np.eye(w, dtype=dtype)
+    X = np.zeros((w, w), dtype=dtype)
+    for i in range(w):
+        X[i] = Bm[i] if (unit and fault != "stored diagonal") else Bm[i] / T[i, i]
+        X[i, i + 1:] = 0
+        Bm[i + 1:] -= np.outer(T[i + 1:, i], X[i])
+    return X
+
+
+def trinv_check(T, Xh, unit, what):
+    """|T X^ - I| <= SAFETY (w + 2) u |T| |X^| elementwise (the residual bound of a substitution), the strict upper triangle of X^
+    exactly +0.0, everything finite.  Returns the worst err / bound."""
+    w = T.shape[0]
+    if not np.all(np.isfinite(Xh)):
+        raise AssertionError(f"{what}: non-finite stored results at {np.argwhere(~np.isfinite(Xh))[:8].tolist()}")
+    up = np.triu(np.ones((w, w), dtype=bool), 1)
+    if np.any(bits(Xh)[up] != 0):
+        raise AssertionError(f"{what}: the strict upper triangle is beyond the bound: it does not hold +0.0")
+    Tl = tri_lower(T, unit)
+    return assert_equations(matmul_ld(Tl, Xh), np.eye(w), np.full(w, (w + 2) / 1.0), matmul_ld(np.abs(Tl), np.abs(Xh)), np.arange(w), what)
+
+
+def small_ref(Tl, unit_l, Pl, Tu, unit_u, Pu, G):
+    """What k_selinv_small / k_lu_selinv_small compute for one unit, in longdouble, with a first-order forward bound.
+        Xl = Tl^-1, Xu = Tu^-1, Yl = Pl Xl, Yu = Pu Xu, Zl = G Yl, Zu = G^T Yu, Scc = Xu^T Xl + Yu^T Zl
+    (Cholesky: both sides are the one L, G symmetric, so Zu = Zl and Scc = Linv^T Linv + Y^T Z).  Each computed stage is the exact
+    operation on its computed inputs plus its own rounding; to first order, with c = SAFETY u and every product's own rounding
+    c (terms + 2) times its absolute product:
+        dX   <= c (w + 2) |X| |T| |X|                              (substitution: the residual bound of T X^ = I times |X|)
+        dY   <= |P| dX + c (w + 2) |P| |X|
+        dZ   <= |G| dY + c (m + 2) |G| |Y|                         (G is input data: exact)
+        dScc <= dXu^T |Xl| + |Xu|^T dXl + c (w + 2) |Xu|^T |Xl| + dYu^T |Zl| + |Yu|^T dZl + c (m + 2) |Yu|^T |Zl|
+    Returns (Zl, dZl, Zu, dZu, Scc, dScc).  The bound is a sum of magnitudes along the chain, so it is only as sharp as the chain is
+    well conditioned: the tests use diagonally dominant T."""
+    c = SAFETY * U
+    w, m = Tl.shape[0], Pl.shape[0]
+    G = np.asarray(G, dtype=LD)
+    side = []
+    for T, unit, P, Gs in ((Tl, unit_l, Pl, G), (Tu, unit_u, Pu, G.T)):
+        Tt = tri_lower(T, unit).astype(LD)
+        X = np.zeros((w, w), dtype=LD)          # T X = I row by row (inner products): not the column sweep of trinv_emulate
+        for i in range(w):
+            X[i, :i] = -(Tt[i, :i] @ X[:i, :i]) / Tt[i, i]
+            X[i, i] = 1 / Tt[i, i]
+        dX = c * (w + 2) * matmul_ld(np.abs(X), matmul_ld(np.abs(Tt), np.abs(X)))
+        P = np.asarray(P, dtype=LD)
+        Y = matmul_ld(P, X)
+        dY = matmul_ld(np.abs(P), dX) + c * (w + 2) * matmul_ld(np.abs(P), np.abs(X))
+        Z = matmul_ld(Gs, Y)
+        dZ = matmul_ld(np.abs(Gs), dY) + c * (m + 2) * matmul_ld(np.abs(Gs), np.abs(Y))
+        side.append((X, dX, Y, dY, Z, dZ))
+    (Xl, dXl, Yl, dYl, Zl, dZl), (Xu, dXu, Yu, dYu, Zu, dZu) = side
+    Scc = matmul_ld(Xu.T, Xl) + matmul_ld(Yu.T, Zl)
+    dScc = (matmul_ld(dXu.T, np.abs(Xl)) + matmul_ld(np.abs(Xu).T, dXl) + c * (w + 2) * matmul_ld(np.abs(Xu).T, np.abs(Xl))
+            + matmul_ld(dYu.T, np.abs(Zl)) + matmul_ld(np.abs(Yu).T, dZl) + c * (m + 2) * matmul_ld(np.abs(Yu).T, np.abs(Zl)))
+    return Zl, dZl, Zu, dZu, Scc, dScc
+
+
+def small_emulate(Tl, unit_l, Pl, Tu, unit_u, Pu, G, fault=None):
+    """float64 emulation of the same chain; returns (Zl, Zu, Scc)"""
+    Xl, Xu = trinv_emulate(Tl, unit_l, fault), trinv_emulate(Tu, unit_u, fault)
+    Yl, Yu = Pl @ Xl, Pu @ Xu
+    Zl, Zu = G @ Yl, G.T @ Yu
+    return Zl, Zu, Xu.T @ Xl + Yu.T @ Zl
+
+
+def logdet_bound(logs):
+    """a 256-leaf tree (8 levels), then ceil(np / 256) terms per lane and the same tree; plus u |log| per term for log itself"""
+    mag = np.sum(np.abs(np.asarray(logs, dtype=LD)))
+    nparts = (len(logs) + 255) // 256
+    return (SAFETY * (8 + (nparts + 255) // 256 + 2) + 1) * U * mag

@@ -63,6 +63,33 @@ struct Dev {
 
 }  // namespace
 
+// host images of the structure arrays of the selected inversion (sf::SelStruct) with their lengths
+struct KpSel {
+    const int32_t *Super, *SuperMap;
+    const int64_t* Lsip;
+    const int32_t* Lsi;
+    const int64_t* Xp;
+    const sf::SelPair* pairs;
+    const int32_t* relmap;
+    int64_t nsuper, n, nLsi, npair, nrel;
+};
+
+namespace {
+
+sf::SelStruct sel_in(Dev& d, const KpSel* h) {
+    sf::SelStruct t;
+    t.Super = d.in(h->Super, h->nsuper + 1);
+    t.SuperMap = d.in(h->SuperMap, h->n);
+    t.Lsip = d.in(h->Lsip, h->nsuper + 1);
+    t.Lsi = d.in(h->Lsi, h->nLsi);
+    t.Xp = d.in(h->Xp, h->nsuper + 1);
+    t.pairs = d.in(h->pairs, h->npair);
+    t.relmap = d.in(h->relmap, h->nrel);
+    return t;
+}
+
+}  // namespace
+
 extern "C" {
 
 int kp_sizeof(const char* name) {
@@ -74,6 +101,8 @@ int kp_sizeof(const char* name) {
     if (!strcmp(name, "SolveTask")) return (int)sizeof(sf::SolveTask);
     if (!strcmp(name, "FillTile")) return (int)sizeof(sf::FillTile);
     if (!strcmp(name, "CondScalars")) return (int)sizeof(sf::CondScalars);
+    if (!strcmp(name, "SelUnit")) return (int)sizeof(sf::SelUnit);
+    if (!strcmp(name, "SelPair")) return (int)sizeof(sf::SelPair);
     return -1;
 }
 
@@ -420,6 +449,144 @@ int kp_load_panels(double* arena, int64_t narena, const int64_t* Lp, const int32
     if (d.rc == hipSuccess) sf::launch_load_panels(dLp, dLi, dLx, n, dS, dSM, dLsip, dLsi, dLsxp, A, skip_diag, dmask, 0);
     d.finish();
     d.out(arena, A, narena);
+    return (int)d.rc;
+}
+
+// ---- the selected inversion (csrc/sf_selinv.hip, csrc/sf_selinv_lu.hip): tests/test_kernels_selinv.py ----
+// The factor (L, or PL / PU) and the arenas of Sigma (S, or SL / SU) are separate images with the same panel offsets; Sigma in and out.
+int kp_selinv_small(const double* L, double* S, int64_t narena, const sf::SelUnit* units, int nunits, const KpSel* sel) {
+    Dev d;
+    const double* dL = d.in(L, narena);
+    double* dS = d.in(S, narena);
+    const sf::SelUnit* U = d.in(units, nunits);
+    const sf::SelStruct t = sel_in(d, sel);
+    if (d.rc == hipSuccess) sf::launch_selinv_small(U, nunits, dL, dS, t, 0);
+    d.finish();
+    d.out(S, dS, narena);
+    return (int)d.rc;
+}
+
+int kp_lu_selinv_small(const double* PL, const double* PU, double* SL, double* SU, int64_t narena, const sf::SelUnit* units, int nunits,
+                       const KpSel* sel) {
+    Dev d;
+    const double* dPL = d.in(PL, narena);
+    const double* dPU = d.in(PU, narena);
+    double* dSL = d.in(SL, narena);
+    double* dSU = d.in(SU, narena);
+    const sf::SelUnit* U = d.in(units, nunits);
+    const sf::SelStruct t = sel_in(d, sel);
+    if (d.rc == hipSuccess) sf::launch_lu_selinv_small(U, nunits, dPL, dPU, dSL, dSU, t, 0);
+    d.finish();
+    d.out(SL, dSL, narena);
+    d.out(SU, dSU, narena);
+    return (int)d.rc;
+}
+
+// lu == 0: k_selinv_trinv; otherwise k_lu_selinv_trinv with `unit`.  out: nout doubles, in and out (the launch writes the first w * w)
+int kp_selinv_trinv(const double* P, int64_t narena, const sf::SelUnit* u, int lu, int unit, double* out, int64_t nout) {
+    Dev d;
+    const double* dP = d.in(P, narena);
+    double* O = d.in(out, nout);
+    if (d.rc == hipSuccess) {
+        if (lu) sf::launch_lu_selinv_trinv(*u, dP, unit, O, 0);
+        else sf::launch_selinv_trinv(*u, dP, O, 0);
+    }
+    d.finish();
+    d.out(out, O, nout);
+    return (int)d.rc;
+}
+
+// A, B and C at offsets of one scratch image `buf` (in and out); a_off < 0: no A (am == 2).  S / S2: the arenas of the gathered
+// operand (am == 2; S2 null: S2 = S), sel: the structure arrays, or null when am != 2
+int kp_selinv_gemm(int am, int M, int N, int K, double* buf, int64_t nbuf, int64_t a_off, int64_t lda, int64_t b_off, int64_t ldb,
+                   int64_t c_off, int64_t ldc, int slabs, int64_t cstride, int acc_in, const sf::SelUnit* u, const double* S, const double* S2,
+                   int64_t narena, const KpSel* sel) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    const double* dS = S ? d.in(S, narena) : nullptr;
+    const double* dS2 = S2 ? d.in(S2, narena) : dS;
+    sf::SelStruct t{};
+    if (sel) t = sel_in(d, sel);
+    if (d.rc == hipSuccess)
+        sf::launch_selinv_gemm(am, M, N, K, a_off < 0 ? nullptr : W + a_off, lda, W + b_off, ldb, W + c_off, ldc, slabs, cstride, acc_in, *u, dS,
+                               dS2, t, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+int kp_selinv_sum(double* buf, int64_t nbuf, int64_t src_off, int nslab, int64_t stride, int64_t count, int64_t dst_off, int acc_in) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    if (d.rc == hipSuccess) sf::launch_selinv_sum(W + src_off, nslab, stride, count, W + dst_off, acc_in, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+// Zu null: k_selinv_finish on S; otherwise k_lu_selinv_finish on (S, SU)
+int kp_selinv_finish(const sf::SelUnit* u, const double* Z, const double* Zu, int64_t nZ, const double* Sc, int64_t nSc, double* S, double* SU,
+                     int64_t narena) {
+    Dev d;
+    const double* dZ = d.in(Z, nZ);
+    const double* dZu = Zu ? d.in(Zu, nZ) : nullptr;
+    const double* dSc = d.in(Sc, nSc);
+    double* dS = d.in(S, narena);
+    double* dSU = Zu ? d.in(SU, narena) : nullptr;
+    if (d.rc == hipSuccess) {
+        if (Zu) sf::launch_lu_selinv_finish(*u, dZ, dZu, dSc, dS, dSU, 0);
+        else sf::launch_selinv_finish(*u, dZ, dSc, dS, 0);
+    }
+    d.finish();
+    d.out(S, dS, narena);
+    if (Zu) d.out(SU, dSU, narena);
+    return (int)d.rc;
+}
+
+// dg: nd doubles, in and out (the launch writes the first n)
+int kp_selinv_diag(int64_t n, const double* S, int64_t narena, const KpSel* sel, int lu, double* dg, int64_t nd) {
+    Dev d;
+    const double* dS = d.in(S, narena);
+    const sf::SelStruct t = sel_in(d, sel);
+    double* D = d.in(dg, nd);
+    if (d.rc == hipSuccess) {
+        if (lu) sf::launch_lu_selinv_diag(n, dS, t, D, 0);
+        else sf::launch_selinv_diag(n, dS, t, D, 0);
+    }
+    d.finish();
+    d.out(dg, D, nd);
+    return (int)d.rc;
+}
+
+// buf: nbuf doubles, in and out: ceil(n / 256) partial sums, then the result (one double; lu: two); neg: the counts (lu only)
+int kp_logdet(int64_t n, const double* P, int64_t narena, const KpSel* sel, int lu, double* buf, int64_t nbuf, int32_t* neg, int64_t nneg) {
+    Dev d;
+    const double* dP = d.in(P, narena);
+    const sf::SelStruct t = sel_in(d, sel);
+    double* B = d.in(buf, nbuf);
+    int32_t* G = lu ? d.in(neg, nneg) : nullptr;
+    if (d.rc == hipSuccess) {
+        if (lu) sf::launch_lu_logdet(n, dP, t, B, G, 0);
+        else sf::launch_logdet(n, dP, t, B, 0);
+    }
+    d.finish();
+    d.out(buf, B, nbuf);
+    if (lu) d.out(neg, G, nneg);
+    return (int)d.rc;
+}
+
+// out: nout doubles, in and out (the launch writes the first e_end - e_begin)
+int kp_lu_selinv_pack(const KpSel* sel, const int64_t* RefXp, const double* SL, const double* SU, int64_t narena, double* out, int64_t nout,
+                      int64_t e_begin, int64_t e_end) {
+    Dev d;
+    const sf::SelStruct t = sel_in(d, sel);
+    const int64_t* RX = d.in(RefXp, sel->nsuper + 1);
+    const double* dSL = d.in(SL, narena);
+    const double* dSU = d.in(SU, narena);
+    double* O = d.in(out, nout);
+    if (d.rc == hipSuccess) sf::launch_lu_selinv_pack(t, RX, (int32_t)sel->nsuper, dSL, dSU, O, e_begin, e_end, 0);
+    d.finish();
+    d.out(out, O, nout);
     return (int)d.rc;
 }
 

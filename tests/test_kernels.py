@@ -40,6 +40,9 @@ SOLVE_TASK = np.dtype([("panel", "<i8"), ("rows", "<i8"), ("ld", "<i4"), ("diag"
                        ("first_col", "<i4"), ("flag", "<i4"), ("expect", "<i4"), ("tdiag", "<i8")])
 FILL_TILE = np.dtype([("xp", "<i8"), ("nsrow", "<i4"), ("r0", "<i4"), ("c0", "<i4"), ("cb", "<i4"), ("ce", "<i4")], align=True)
 COND_SCALARS = np.dtype([("nrm", "<f8"), ("flags", "<i4"), ("j", "<i4")])
+SEL_UNIT = np.dtype([("lx", "<i8"), ("rows", "<i8"), ("nsrow", "<i4"), ("ncol", "<i4"), ("cb", "<i4"), ("w", "<i4"), ("pair0", "<i4"),
+                     ("npair", "<i4")])
+SEL_PAIR = np.dtype([("map_off", "<i8"), ("i", "<i4"), ("pad_", "<i4")])
 
 
 def _make(args, timeout):
@@ -54,7 +57,8 @@ def test_probe_compiles(tmp_path):
     nm = subprocess.run(["nm", "-D", str(tmp_path / "libsf_kprobe.so")], stdout=subprocess.PIPE, text=True).stdout
     for name in ("kp_gemm", "kp_update_small", "kp_potrf", "kp_getrf", "kp_trsm", "kp_step", "kp_build_loadmap", "kp_solve_fwd",
                  "kp_solve_bwd", "kp_pack_lu", "kp_lu_fill_u11", "kp_factor_hash", "kp_tsolve_bwd", "kp_condest_fill", "kp_condest_sign_norm",
-                 "kp_condest_argmax_next", "kp_solve_many_pack", "kp_solve_many_unpack"):
+                 "kp_condest_argmax_next", "kp_solve_many_pack", "kp_solve_many_unpack", "kp_selinv_small", "kp_lu_selinv_small",
+                 "kp_selinv_trinv", "kp_selinv_gemm", "kp_selinv_sum", "kp_selinv_finish", "kp_selinv_diag", "kp_logdet", "kp_lu_selinv_pack"):
         assert f" T {name}" in nm
 
 
@@ -234,7 +238,8 @@ def kp():
     assert r.returncode == 0, r.stdout
     L = C.CDLL(os.path.join(KDIR, "libsf_kprobe.so"))
     for name, dt in (("GemmProb", GEMM_PROB), ("GemmTask", GEMM_TASK), ("PotrfTask", POTRF_TASK), ("TrsmTask", TRSM_TASK), ("StepTask", STEP_TASK),
-                     ("SolveTask", SOLVE_TASK), ("FillTile", FILL_TILE), ("CondScalars", COND_SCALARS)):
+                     ("SolveTask", SOLVE_TASK), ("FillTile", FILL_TILE), ("CondScalars", COND_SCALARS), ("SelUnit", SEL_UNIT),
+                     ("SelPair", SEL_PAIR)):
         assert L.kp_sizeof(name.encode()) == dt.itemsize, name
     vp, i64, i32, f64 = C.c_void_p, C.c_int64, C.c_int, C.c_double
     L.kp_gemm.argtypes = [vp, i64, vp, i32, vp, i32, vp, C.c_uint32, C.c_uint32, i32, vp, i64, i32, i32, i32]
