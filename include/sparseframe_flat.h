@@ -511,6 +511,46 @@ int sf_lu_plan_solve_many(sf_lu_plan *plan, sf_long nrhs, const sf_float *B, sf_
  * plan whose last started factorization has not succeeded (as sf_lu_plan_refine). */
 int sf_lu_plan_solve_transposed(sf_lu_plan *plan, const sf_float *b_host, sf_float *x_host);
 int sf_lu_plan_solve_many_transposed(sf_lu_plan *plan, sf_long nrhs, const sf_float *B, sf_long ldb, sf_float *X, sf_long ldx);
+/* ---- half solves and C^T A^{-1} B for LU plans.  Permuted space.  A = L U in the plan's panels; F is what the forward
+ * sweep of sf_lu_plan_solve applies: F = L^{-1} without pivoting, F = E_K^{-1} P_K ... E_1^{-1} P_1 with it (the interchanges block
+ * by block, see sf_lu_plan_set_pivoting).  So A^{-1} = U^{-1} F and A^{-T} = F^T U^{-T}. ---- */
+/* One half of a solve on its own: SF_LU_HALF_L then SF_LU_HALF_U is sf_lu_plan_solve_many, SF_LU_HALF_UT then SF_LU_HALF_LT is
+ * sf_lu_plan_solve_many_transposed (e.g. the two sides of a split preconditioner).  Arguments, the chunks of 16, the in-place rule
+ * (X == B needs ldx == ldb), the one-column kernels for nrhs == 1 and the stat "last_half_ms" as sf_chol_plan_solve_half; the
+ * kernels are those of sf_lu_plan_solve[_many][_transposed].  The two backward halves (U, LT) make their row-major copies of the
+ * wide diagonal blocks on the first chunk of every call, from the U^T panels and from the L panels respectively.  nrhs == 0: no-op.
+ * NULL pointers, any other `which`, nrhs < 0, a short leading dimension, Cholesky plans, schedule-only, partial, sharded, mapped
+ * and out-of-core plans and a plan whose last started factorization has not succeeded: SF_ERR_ARG, nothing written. */
+#define SF_LU_HALF_L  0   /* X <- F B       forward sweep over the L panels, unit diagonal, the interchanges applied   */
+#define SF_LU_HALF_U  1   /* X <- U^{-1} B  backward sweep over the U^T panels                                         */
+#define SF_LU_HALF_UT 2   /* X <- U^{-T} B  forward sweep over the U^T panels, no interchanges                         */
+#define SF_LU_HALF_LT 3   /* X <- F^T B     backward sweep over the L panels, the interchanges undone                  */
+int sf_lu_plan_solve_half(sf_lu_plan *plan, int which, sf_long nrhs,
+                          const sf_float *B, sf_long ldb, sf_float *X, sf_long ldx);
+/* G = C^T A^{-1} B for an n x m block C and an n x k block B (m, k <= SF_GRAM_MAX_K): with Z = U^{-T} C and Y = F B, G = Z^T Y --
+ * two FORWARD sweeps per pair of chunks and no backward one.  Every chunk of 16 columns of C is swept into its Z block first; then
+ * each chunk of B is swept into its Y block and its chunk column of G, the tiles Z_a^T Y_b for every a, is reduced at once with
+ * v_mfma_f64_16x16x4_f64.  Z and Y never leave the device; m x k doubles come back.  m == k == 1 runs the one-column sweeps on two
+ * n-vectors and a dot product.  C, B: column-major, ldc, ldb >= max(n, 1), both read only (C == B is allowed: B^T A^{-1} B, which
+ * is NOT symmetric for an unsymmetric A).  G: column-major m x k, ldg >= max(m, 1), nothing outside the m x k entries is written.
+ * m == 0 or k == 0: SF_OK, nothing written; n == 0: zeros.  Refusals as sf_lu_plan_solve_half, and m or k negative or above
+ * SF_GRAM_MAX_K.
+ * Determinism: the reductions use no floating-point atomics and a fixed order, so for given Z and Y the result repeats bit for
+ * bit; entry (i, j) is a function of column i of C and column j of B alone, so a NaN or Inf in column j of B reaches column j
+ * of G only and one in column i of C row i of G only.  G is not symmetric, and two calls agree to rounding only where the sweeps
+ * scatter with atomics (bit for bit where a sweep has nothing to reorder).
+ * The store -- ceil(m / 16) Z blocks and ceil(k / 16) Y blocks of n x 16 doubles, the parts of one chunk column, the padded result
+ * block of the host call -- is allocated or grown by the first call that needs it and kept: "bytes_gram" (not in "bytes_device");
+ * SF_ERR_ALLOC leaves the plan and a smaller store as they were.  "last_gram_ms", "last_gram_parts" as sf_chol_plan_gram (parts: 0
+ * on the one-column path). */
+int sf_lu_plan_gram(sf_lu_plan *plan, sf_long m, const sf_float *C, sf_long ldc,
+                    sf_long k, const sf_float *B, sf_long ldb, sf_float *G, sf_long ldg);   /* host, column-major */
+/* the same on device memory: pointer checks (over the spans of all three blocks) and synchronisation as sf_chol_plan_gram_device;
+ * dG must overlap neither input (SF_ERR_ARG).  flags: 0 or SF_DEV_PERM_IN -- BOTH inputs are then in the caller's numbering, the one
+ * ordering of sf_lu_plan_set_ordering. */
+int sf_lu_plan_gram_device(sf_lu_plan *plan, int flags /* 0 | SF_DEV_PERM_IN */,
+                           sf_long m, const sf_float *dC, sf_long ldc,
+                           sf_long k, const sf_float *dB, sf_long ldb, sf_float *dG, sf_long ldg);
 /* the device-pointer entry points for an LU plan (see sf_chol_plan_set_ordering and below): op is SF_OP_SOLVE or SF_OP_TRANS, both with
  * the plan's interchanges when pivoting is on; set_values_device takes dUx as sf_lu_plan_set_values takes Ux (NULL when U aliases
  * L) and finds max |a_ij|, the scale of the pivot perturbation, on the device.  A Cholesky plan is refused (SF_ERR_ARG). */

@@ -275,6 +275,13 @@ lib.sf_lu_plan_solve_transposed.argtypes = [C.c_void_p, c_double_p, c_double_p]
 lib.sf_lu_plan_solve_transposed.restype = C.c_int
 lib.sf_lu_plan_solve_many_transposed.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64]
 lib.sf_lu_plan_solve_many_transposed.restype = C.c_int
+lib.sf_lu_plan_solve_half.argtypes = [C.c_void_p, C.c_int, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64]
+lib.sf_lu_plan_solve_half.restype = C.c_int
+lib.sf_lu_plan_gram.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64]
+lib.sf_lu_plan_gram.restype = C.c_int
+lib.sf_lu_plan_gram_device.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.c_int64]
+lib.sf_lu_plan_gram_device.restype = C.c_int
 for _n in ("sf_chol_plan_condest", "sf_lu_plan_condest"):
     getattr(lib, _n).argtypes = [C.c_void_p, c_double_p, c_double_p]
     getattr(lib, _n).restype = C.c_int

@@ -50,6 +50,30 @@ def _solve_many(fn, name, h, n, B):
     return X
 
 
+def _lu_solve_guarded(S, r, message):
+    """S^-1 r by LU with partial pivoting on the host (S: (k, k), small).  ValueError(message) when S is singular: a zero pivot, one
+    that is not finite, or one below 8 k eps of the largest entry its column of S had before the elimination -- a pivot that
+    rounding alone could have produced; the solution would be noise"""
+    A = np.array(S, dtype=np.float64)
+    y = np.array(r, dtype=np.float64)
+    k = A.shape[0]
+    floor = 8 * k * np.finfo(np.float64).eps * np.abs(A).max(axis=0)
+    for j in range(k):
+        p = j + int(np.argmax(np.abs(A[j:, j])))
+        piv = A[p, j]
+        if not np.isfinite(piv) or abs(piv) <= floor[j]:
+            raise ValueError(message)
+        if p != j:
+            A[[j, p]] = A[[p, j]]
+            y[[j, p]] = y[[p, j]]
+        l = A[j + 1:, j] / piv
+        A[j + 1:, j + 1:] -= np.outer(l, A[j, j + 1:])
+        y[j + 1:] -= l * y[j]
+    for j in range(k - 1, -1, -1):
+        y[j] = (y[j] - A[j, j + 1:] @ y[j + 1:]) / A[j, j]
+    return y
+
+
 def device_count():
     return int(lib.sf_device_count())
 
@@ -966,6 +990,104 @@ class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _C
         if trans:
             return _solve_many(lib.sf_lu_plan_solve_many_transposed, "sf_lu_plan_solve_many_transposed", self._h, self.n, B)
         return _solve_many(lib.sf_lu_plan_solve_many, "sf_lu_plan_solve_many", self._h, self.n, B)
+
+    def _block(self, B, what):
+        """1-D or (n, k) input in any memory order -> (column-major float64 (n, k), was 1-D)"""
+        B = np.asarray(B)
+        one = B.ndim == 1
+        if one:
+            B = B.reshape(-1, 1)
+        if B.ndim != 2 or B.shape[0] != self.n:
+            raise ValueError(f"{what}: block must have shape ({self.n},) or ({self.n}, k), got {B.shape}")
+        return np.asfortranarray(B, dtype=np.float64), one
+
+    _HALVES = {"L": 0, "U": 1, "Ut": 2, "Lt": 3}        # SF_LU_HALF_*
+    GRAM_MAX_K = 1024       # SF_GRAM_MAX_K
+
+    def half_solve(self, B, which="L"):
+        """one half of a solve with the resident factor (A = L U, permuted space; F = what the forward sweep of solve applies,
+        L^-1 with the plan's interchanges): F B (which="L"), U^-1 B ("U"), U^-T B ("Ut") or F^T B ("Lt").  "L" then "U" is
+        solve_many, "Ut" then "Lt" is solve_many(trans=True).  B: (n,) or (n, k) in any memory order"""
+        if which not in self._HALVES:
+            raise ValueError(f"half_solve: which must be one of 'L', 'U', 'Ut', 'Lt', got {which!r}")
+        Bf, one = self._block(B, "half_solve")
+        k, ld = Bf.shape[1], max(self.n, 1)
+        X = np.empty((self.n, k), dtype=np.float64, order="F")
+        if k:
+            check(lib.sf_lu_plan_solve_half(self._h, self._HALVES[which], k, _dp(Bf), ld, _dp(X), ld), "sf_lu_plan_solve_half")
+        return X[:, 0] if one else X
+
+    def cross_gram(self, C, B):
+        """G = C^T A^-1 B for the blocks C (n, m) and B (n, k) in any memory order (permuted space): two forward sweeps per pair
+        of 16-column chunks and a reduction on the device, only the (m, k) result comes back.  Not symmetric, even for C is B.
+        Two 1-D inputs give the float c^T A^-1 b.  m, k <= 1024"""
+        Cf, onec = self._block(C, "cross_gram")
+        Bf, oneb = self._block(B, "cross_gram")
+        m, k = Cf.shape[1], Bf.shape[1]
+        if m > self.GRAM_MAX_K or k > self.GRAM_MAX_K:
+            raise ValueError(f"cross_gram: at most {self.GRAM_MAX_K} columns a block, got {m} and {k}")
+        G = np.zeros((m, k), dtype=np.float64, order="F")
+        if m and k:
+            ld = max(self.n, 1)
+            check(lib.sf_lu_plan_gram(self._h, m, _dp(Cf), ld, k, _dp(Bf), ld, _dp(G), m), "sf_lu_plan_gram")
+        return float(G[0, 0]) if (onec and oneb) else G
+
+    def cross_gram_device(self, C, B, out=None, perm_in=False):
+        """cross_gram(C, B) for device tensors ((n,) or column-major (n, m) / (n, k)) into a device tensor: out (column-major
+        (m, k), overlapping neither input) or a new one.  perm_in: C and B are in the caller's numbering (set_ordering)"""
+        C, m, ldc, _ = _dev_tensor(C, self.n, self.device, "cross_gram_device (C)")
+        B, k, ldb, _ = _dev_tensor(B, self.n, self.device, "cross_gram_device (B)")
+        if m > self.GRAM_MAX_K or k > self.GRAM_MAX_K:
+            raise ValueError(f"cross_gram_device: at most {self.GRAM_MAX_K} columns a block, got {m} and {k}")
+        torch = None
+        if out is None:
+            torch = self._dev_sync()
+            out = torch.empty_strided((m, k), (1, max(m, 1)), dtype=torch.float64, device=f"cuda:{self.device}")
+        G, kg, ldg, oneg = _dev_tensor(out, m, self.device, "cross_gram_device (out)", writable=True)
+        if oneg or kg != k:
+            raise ValueError(f"cross_gram_device: out must have shape ({m}, {k}), got {tuple(out.shape)}")
+        if m and k:
+            if torch is None:
+                self._dev_sync()
+            check(lib.sf_lu_plan_gram_device(self._h, 1 if perm_in else 0, m, C.data_ptr(), ldc, k, B.data_ptr(), ldb, G.data_ptr(), ldg),
+                  "sf_lu_plan_gram_device")
+        return out
+
+    def schur_complement(self, C, B, D):
+        """the Schur complement D - C^T A^-1 B of the bordered matrix [[A, B], [C^T, D]] (C: (n, m), B: (n, k), D: (m, k))"""
+        Cf, _ = self._block(C, "schur_complement")
+        Bf, _ = self._block(B, "schur_complement")
+        D = np.asarray(D, dtype=np.float64)
+        if D.shape != (Cf.shape[1], Bf.shape[1]):
+            raise ValueError(f"schur_complement: D must have shape ({Cf.shape[1]}, {Bf.shape[1]}), got {D.shape}")
+        return D - self.cross_gram(Cf, Bf)
+
+    def solve_saddle(self, B, C, f, g, D=None):
+        """(x, y) with [[A, B], [C^T, -D]] [x; y] = [f; g] (an unsymmetric bordered system; permuted space): B, C (n, k), f (n,),
+        g (k,), D (k, k) or None = 0.  One cross_gram(C, [B f]) gives S0 = C^T A^-1 B and t = C^T A^-1 f; S = D + S0 is solved on
+        the host by LU with partial pivoting, y = S^-1 (t - g), x = solve(f - B y): no (n, k) block comes back.  A singular S --
+        exactly, or with a pivot below 8 k eps of the largest entry its column had before the elimination -- raises ValueError"""
+        Bf, oneb = self._block(B, "solve_saddle")
+        Cf, onec = self._block(C, "solve_saddle")
+        k = Bf.shape[1]
+        f = _f64(f)
+        g = np.asarray(g, dtype=np.float64).reshape(-1)
+        if oneb or onec or Cf.shape[1] != k or f.shape != (self.n,) or g.shape != (k,):
+            raise ValueError(f"solve_saddle: B, C, f, g must have shapes ({self.n}, k), ({self.n}, k), ({self.n},), (k,), got "
+                             f"{np.shape(B)}, {np.shape(C)}, {f.shape}, {g.shape}")
+        if D is not None:
+            D = np.asarray(D, dtype=np.float64)
+            if D.shape != (k, k):
+                raise ValueError(f"solve_saddle: D must have shape ({k}, {k}), got {D.shape}")
+        if k + 1 > self.GRAM_MAX_K:
+            raise ValueError(f"solve_saddle: at most {self.GRAM_MAX_K - 1} border columns, got {k}")
+        G = self.cross_gram(Cf, np.column_stack([Bf, f]))
+        S, t = G[:, :k], G[:, k]
+        if D is not None:
+            S = S + D
+        y = _lu_solve_guarded(S, t - g, "solve_saddle: D + C^T A^-1 B is singular (a singular Schur complement)") if k else np.zeros(0)
+        x = self.solve(f - Bf @ y)
+        return x, y
 
     def selinv(self):
         """selected inversion: A^-1 on the pattern of L + U into a pair of device arenas (permuted space), from the resident

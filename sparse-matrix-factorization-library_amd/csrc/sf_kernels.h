@@ -241,6 +241,14 @@ int gram_slabs(int64_t n, int64_t* slab_rows);
 // Y: the chunks 0 .. a, chunk c the row-major n x SVM_W block at c * n * SVM_W; part: (a + 1) x gram_slabs x 256 doubles
 void launch_gram_row(const double* Y, int64_t n, int a, int64_t k, double* part, double* G, int64_t ldg, hipStream_t st);
 
+// ---- C^T A^{-1} B = Z^T Y with an LU plan (sf_gram_lu.hip, sf_lu_plan_gram) ----
+// chunk column b of G = Z^T Y: the tiles (0 .. nza - 1, b) into the column-major m x k result G (leading dimension ldg).  Z: nza
+// row-major n x SVM_W blocks, block a at a * n * SVM_W; Yb: the one block of chunk b; part: nza x gram_slabs x 256 doubles
+void launch_gram2_col(const double* Z, const double* Yb, int64_t n, int nza, int b, int64_t m, int64_t k, double* part, double* G,
+                      int64_t ldg, hipStream_t st);
+// *out = sum_i x[i] y[i], two passes in a fixed order; scratch: QF_MAXB parts, out may follow them
+void launch_dot(const double* x, const double* y, int64_t n, double* scratch, double* out, hipStream_t st);
+
 // ---- selected inversion (sf_selinv.hip, sf_chol_plan_selinv) ----
 // one unit: columns [cb, cb + w) of the supernode whose panel starts at lx (factor and arena share the layout), rows at Lsi[rows ..]
 struct SelUnit {

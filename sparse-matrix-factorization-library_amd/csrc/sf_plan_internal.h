@@ -145,6 +145,11 @@ int sf_refine_anorm(sf_chol_plan* p, const double** d_anorm, hipStream_t st);
 // ---- shared with the device-pointer solves (sf_device_io.hip) ----
 // x <- A^{-T} x for an LU plan (sf_solve_t.hip; the caller has zeroed the sync block on the stream)
 void tsolve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, hipStream_t st);
+// its two halves (shared with the LU half solves and C^T A^{-1} B, sf_gram_lu.hip): x <- U^{-T} x, the forward sweep over the U^T
+// panels, and x <- F^T x, the backward sweep over the L panels with the interchanges undone (transpose_diag: its row-major
+// diagonal copies, made from the L panels)
+void tsolve_sweep_fwd(sf_chol_plan* p, double* x, int width, const SolveSync& y, hipStream_t st);
+void tsolve_sweep_bwd(sf_chol_plan* p, double* x, int width, bool transpose_diag, const SolveSync& y, hipStream_t st);
 // ---- shared with the Gram matrix (sf_gram.hip) ----
 // `ptr` is device (or managed) memory of the plan's device with room for `doubles` doubles from there on (sf_device_io.hip)
 bool sf_device_ptr_ok(const sf_chol_plan* p, const void* ptr, size_t doubles);
@@ -281,8 +286,10 @@ struct sf_chol_plan {
     // sf_chol_plan_gram / _gram_device (sf_gram.hip): the Y store -- gram_chunks row-major n x SVM_W blocks, the parts of one chunk
     // row, the result block of the host-array call -- allocated or grown by the first call that needs it (bytes_gram, not in
     // bytes_device); last_gram_parts: slabs per tile of the last call (0: the one-column path)
+    // sf_lu_plan_gram / _gram_device (sf_gram_lu.hip): the same store holds gram_chunks Z blocks, gram_chunks_y Y blocks, the parts of
+    // one chunk column and the padded result block
     double* d_gram = nullptr;
-    int64_t gram_chunks = 0;
+    int64_t gram_chunks = 0, gram_chunks_y = 0;
     size_t bytes_gram = 0;
     double last_gram_ms = 0;
     int last_gram_parts = 0;

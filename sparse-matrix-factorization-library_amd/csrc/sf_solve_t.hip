@@ -447,27 +447,29 @@ bool tsolve_refused(const sf_chol_plan* p) {
 
 }  // namespace
 
-// x <- A^{-T} x for an LU plan (the caller has zeroed the sync block on the stream).  The row-major copies of the top steps'
-// diagonal blocks (d_solveT) are made from the PL base here, on every call that asks for them; their diagonal entries are copied
-// too and simply not read.  sf_solve_sweep_bwd remakes them from PU at the start of every solve / solve_many / refine call, so
-// neither sweep ever sees the other's copies -- keep it that way: a caller that alternates the two (the condition estimate)
-// must ask BOTH for their copies every time.
-void tsolve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, hipStream_t st) {
-    const SolveSync y = sf_solve_sync(p);
-    const double* PL = p->d_Lsx;
+// x <- A^{-T} x for an LU plan (the caller has zeroed the sync block on the stream), in its two halves.  The row-major copies of the
+// top steps' diagonal blocks (d_solveT) are made from the PL base by the second half, on every call that asks for them; their
+// diagonal entries are copied too and simply not read.  sf_solve_sweep_bwd remakes them from PU at the start of every solve /
+// solve_many / refine call, so neither sweep ever sees the other's copies -- keep it that way: a caller that alternates the two
+// (the condition estimate, the half solves of sf_gram_lu.hip) must ask BOTH for their copies every time.
+// (U^T)^{-1}: the plain forward kernels on the other panel set -- non-unit diagonal, no interchanges
+void tsolve_sweep_fwd(sf_chol_plan* p, double* x, int width, const SolveSync& y, hipStream_t st) {
     const double* PU = p->d_Lsx + p->xC;
-    const int32_t* piv = p->piv_tol > 0.0 ? p->d_piv : nullptr;
     const size_t nsteps = p->solve_steps.size();
-    // (U^T)^{-1}: the plain forward kernels on the other panel set -- non-unit diagonal, no interchanges
     for (size_t k = 0; k < nsteps; ++k) {
         const auto& s = p->solve_steps[k];
         int* tk = y.tickets + sf_chol_plan::SOLVE_TICKETS * k;
         if (s.small) sf::launch_solve_small_fwd(p->d_solve + s.fwd_first, s.ndiag, width, PU, p->d_Lsi, x, 0, nullptr, st);
         else sf::launch_solve_fwd(p->d_solve + s.fwd_first, s.fwd_count, width, s.big, PU, p->d_Lsi, x, 0, nullptr, y.sync, tk, y.info, st);
     }
-    // L^{-T} with the interchanges undone block by block: sf_solve_step_bwd's launches, the twin kernels
+}
+
+// L^{-T} with the interchanges undone block by block: sf_solve_step_bwd's launches, the twin kernels
+void tsolve_sweep_bwd(sf_chol_plan* p, double* x, int width, bool transpose_diag, const SolveSync& y, hipStream_t st) {
+    const double* PL = p->d_Lsx;
+    const int32_t* piv = p->piv_tol > 0.0 ? p->d_piv : nullptr;
     if (transpose_diag) sf::launch_solve_transpose_diag(p->d_solve, p->d_solveT_list, p->n_solveT, PL, p->d_solveT, st);
-    for (size_t k = nsteps; k-- > 0;) {
+    for (size_t k = p->solve_steps.size(); k-- > 0;) {
         const auto& s = p->solve_steps[k];
         int* tk = y.tickets + sf_chol_plan::SOLVE_TICKETS * k;
         if (s.small) {
@@ -480,6 +482,12 @@ void tsolve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, h
                                   tk + 2, y.info, st, p->d_solveT);
         }
     }
+}
+
+void tsolve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, hipStream_t st) {
+    const SolveSync y = sf_solve_sync(p);
+    tsolve_sweep_fwd(p, x, width, y, st);
+    tsolve_sweep_bwd(p, x, width, transpose_diag, y, st);
 }
 
 namespace {
