@@ -128,8 +128,8 @@ int sf_chol_plan_solve(sf_chol_plan *plan, const sf_float *b_host, sf_float *x_h
  * (LU plans: (L U)^{-1} B, with the plan's pivots when pivoting is on).  B, X: column-major host arrays, leading dimensions
  * ldb, ldx >= n; X may be B (ldx == ldb).  nrhs == 0: no-op.  Whole, resident plans only (partial, sharded, mapped,
  * out-of-core and schedule-only plans: SF_ERR_ARG).  16 right-hand sides per sweep (stat "solve_many_width"); the device
- * block is allocated by the first call and kept (stat "bytes_solve_many", not in "bytes_device"); "last_solve_many_ms":
- * device time of the sweeps of the last call, copies excluded. */
+ * block is allocated by the first call and kept (stat "bytes_solve_many", not in "bytes_device"; SF_ERR_ALLOC leaves the
+ * plan usable); "last_solve_many_ms": device time of the sweeps of the last call, copies excluded. */
 int sf_chol_plan_solve_many(sf_chol_plan *plan, sf_long nrhs, const sf_float *B, sf_long ldb, sf_float *X, sf_long ldx);
 /* values [e_begin, e_end) of the factor in the reference layout (whole plans only) */
 int sf_chol_plan_get_factor_range(sf_chol_plan *plan, sf_long e_begin, sf_long e_end, sf_float *out);
@@ -506,7 +506,8 @@ int sf_lu_plan_solve(sf_lu_plan *plan, const sf_float *b_host, sf_float *x_host)
 int sf_lu_plan_solve_many(sf_lu_plan *plan, sf_long nrhs, const sf_float *B, sf_long ldb, sf_float *X, sf_long ldx);
 /* the transposed solves with the SAME resident factor: x <- A^{-T} b = L^{-T} U^{-T} b, permuted space, the plan's interchanges undone
  * block by block when pivoting is on (no second analysis or factorization of A^T).  Arguments, chunking, layouts, the in-place
- * rule and the stats ("last_solve_ms", "last_solve_many_ms") as sf_lu_plan_solve / sf_lu_plan_solve_many.  NULL arguments,
+ * rule and the stats ("last_solve_ms", "last_solve_many_ms") as sf_lu_plan_solve / sf_lu_plan_solve_many (the device
+ * block of the _many form too: allocated by whichever call comes first, SF_ERR_ALLOC leaves the plan usable).  NULL arguments,
  * Cholesky plans (A = A^T: use the plain solve), schedule-only, partial, sharded, mapped and out-of-core plans: SF_ERR_ARG; so is a
  * plan whose last started factorization has not succeeded (as sf_lu_plan_refine). */
 int sf_lu_plan_solve_transposed(sf_lu_plan *plan, const sf_float *b_host, sf_float *x_host);

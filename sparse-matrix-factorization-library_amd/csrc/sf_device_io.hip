@@ -114,7 +114,7 @@ void launch_dev_load1(const double* B, const int32_t* perm, int64_t n, double* x
     if (perm) hipLaunchKernelGGL(k_dev_load1<true>, g, dim3(256), 0, st, B, perm, n, x);
     else hipLaunchKernelGGL(k_dev_load1<false>, g, dim3(256), 0, st, B, perm, n, x);
 }
-static void launch_dev_store1(const double* x, const int32_t* perm, int64_t n, double* X, hipStream_t st) {
+void launch_dev_store1(const double* x, const int32_t* perm, int64_t n, double* X, hipStream_t st) {
     const dim3 g((unsigned)((n + 255) / 256));
     if (perm) hipLaunchKernelGGL(k_dev_store1<true>, g, dim3(256), 0, st, x, perm, n, X);
     else hipLaunchKernelGGL(k_dev_store1<false>, g, dim3(256), 0, st, x, perm, n, X);
@@ -124,7 +124,7 @@ void launch_dev_pack(const double* B, int64_t ldb, const int32_t* perm, int64_t 
     if (perm) hipLaunchKernelGGL(k_dev_pack<true>, g, dim3(256), 0, st, B, ldb, perm, n, cw, X);
     else hipLaunchKernelGGL(k_dev_pack<false>, g, dim3(256), 0, st, B, ldb, perm, n, cw, X);
 }
-static void launch_dev_unpack(const double* X, const int32_t* perm, int64_t n, int cw, double* D, int64_t ldx, hipStream_t st) {
+void launch_dev_unpack(const double* X, const int32_t* perm, int64_t n, int cw, double* D, int64_t ldx, hipStream_t st) {
     const dim3 g((unsigned)((n + DIO_ROWS - 1) / DIO_ROWS));
     if (perm) hipLaunchKernelGGL(k_dev_unpack<true>, g, dim3(256), 0, st, X, perm, n, cw, D, ldx);
     else hipLaunchKernelGGL(k_dev_unpack<false>, g, dim3(256), 0, st, X, perm, n, cw, D, ldx);
@@ -137,116 +137,28 @@ static void launch_dev_unpack(const double* X, const int32_t* perm, int64_t n, i
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
-// the plans these entry points run on: whole and resident (what sf_chol_plan_solve_many accepts, sharded parts left out too)
-bool dio_refused(const sf_chol_plan* p) {
-    return p->dry || p->partial || p->nranks > 1 || p->ooc_groups > 1 || (p->nsuper > 0 && !p->d_solve);
-}
-
-// `ptr` is device (or managed) memory of the plan's device with room for `doubles` doubles from there on.  Decided on the host,
-// before anything is enqueued: a host pointer never reaches a kernel.  (hipPointerGetAttributes fails for ordinary host memory on
-// some runtimes and reports it as unregistered on others; either way it is refused and no error is left behind.)
-bool dio_device_ptr(const sf_chol_plan* p, const void* ptr, size_t doubles) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, ptr) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    if (a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeManaged) return false;
-    if (a.device != p->device) return false;
-    void* base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)ptr) != hipSuccess) {
-        (void)hipGetLastError();
-        return true;        // (no range to be had for this kind of memory: the attributes have spoken)
-    }
-    const char* end = (const char*)base + size;
-    return (const char*)ptr >= (const char*)base && (size_t)(end - (const char*)ptr) >= doubles * sizeof(double);
-}
-
-// doubles a column-major block of nrhs columns spans
-size_t dio_span(int64_t n, sf_long nrhs, sf_long ld) { return nrhs > 0 ? (size_t)(nrhs - 1) * (size_t)ld + (size_t)n : 0; }
-
-int dio_alloc(void** ptr, size_t bytes) {
-    if (hipMalloc(ptr, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        *ptr = nullptr;
-        return SF_ERR_ALLOC;
-    }
-    return SF_OK;
-}
-
-// the n x SVM_W row-major block (and the staging half the host-array calls use: one allocation, whichever call comes first)
-int dio_block(sf_chol_plan* p) {
-    if (p->d_xm) return SF_OK;
-    const size_t bytes = 2 * (size_t)p->n * sf::SVM_W * sizeof(double);
-    if (int rc = dio_alloc((void**)&p->d_xm, bytes)) return rc;
-    p->bytes_solve_many = bytes;
-    return SF_OK;
-}
-
 enum { DIO_PERMUTE = -1 };      // not an op of the ABI: load and store with nothing in between
-
-// the sweeps of `op` on x (the sync block is cleared here); first: the first chunk of the call
-int dio_sweeps(sf_chol_plan* p, int op, double* x, int width, bool first, hipStream_t st) {
-    if (op == DIO_PERMUTE) return SF_OK;
-    const SolveSync y = sf_solve_sync(p);
-    HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, y.bytes, st));
-    switch (op) {
-        case SF_OP_SOLVE: sf_solve_sweeps(p, x, width, first, st); break;
-        case SF_OP_TRANS: tsolve_sweeps(p, x, width, first, st); break;
-        case SF_OP_HALF_L:
-            for (size_t k = 0; k < p->solve_steps.size(); ++k) sf_solve_step_fwd(p, k, p->d_Lsx, x, width, y, st);
-            break;
-        default: sf_solve_sweep_bwd(p, x, width, first, y, st); break;      // SF_OP_HALF_LT: no forward half has made the copies
-    }
-    return SF_OK;
-}
 
 // load -> sweeps -> store for nrhs columns; pin / pout: the ordering for the way in / out, or null.  *total_ms: device time from
 // the first to the last kernel of every chunk.
 int dio_run(sf_chol_plan* p, int op, const int32_t* pin, const int32_t* pout, sf_long nrhs, const double* dB, sf_long ldb, double* dX,
             sf_long ldx, double* total_ms) {
-    hipStream_t st = p->stream;
-    const int64_t n = p->n;
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    *total_ms = 0;
-    const bool sweeps = op != DIO_PERMUTE;
-    if (nrhs == 1) {
-        // the one-column family on d_x: a lone column is never padded to SVM_W
-        HIP_TRY(hipEventRecord(e0, st));
-        sf::launch_dev_load1(dB, pin, n, p->d_x, st);
-        if (int rc = dio_sweeps(p, op, p->d_x, 1, true, st)) return rc;
-        sf::launch_dev_store1(p->d_x, pout, n, dX, st);
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        if (sweeps) {
-            if (int rc = sf_solve_finish(p, st)) return rc;
-        } else {
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        float ms = 0;
-        if (elapsed_ms(&ms, e0, e1)) *total_ms += ms;
-        return SF_OK;
+    const int W = nrhs == 1 ? 1 : sf::SVM_W;        // (a lone column is never padded to SVM_W: the one-column family on d_x)
+    if (W > 1)
+        if (int rc = sf_solve_many_block(p)) return rc;
+    const SfCols src{const_cast<double*>(dB), ldb, true, pin}, dst{dX, ldx, true, pout};
+    const SfApply a{&src, &dst, nrhs, W, W == 1 ? p->d_x : p->d_xm, 0, op != DIO_PERMUTE};
+    SfStretch t{p};
+    int rc;
+    if (op == DIO_PERMUTE) {
+        rc = sf_apply_chunks(p, a, t, [](double*, sf_long, int) { return SF_OK; });
+    } else {
+        const SfSweep sweep = op == SF_OP_SOLVE ? SF_SWEEP_SOLVE : op == SF_OP_TRANS ? SF_SWEEP_TRANS : op == SF_OP_HALF_L ? SF_SWEEP_FWD_L : SF_SWEEP_BWD;
+        // (the diagonal blocks' row-major copies: once per call; SF_OP_HALF_LT: no forward half has made them)
+        rc = sf_apply_chunks(p, a, t, [&](double* x, sf_long j0, int) { return sf_apply_sweep(p, sweep, x, W, j0 == 0); });
     }
-    if (int rc = dio_block(p)) return rc;
-    const int W = sf::SVM_W;
-    for (sf_long j0 = 0; j0 < nrhs; j0 += W) {
-        const int cw = (int)std::min<sf_long>(W, nrhs - j0);
-        HIP_TRY(hipEventRecord(e0, st));
-        sf::launch_dev_pack(dB + j0 * ldb, ldb, pin, n, cw, p->d_xm, st);
-        if (int rc = dio_sweeps(p, op, p->d_xm, W, j0 == 0, st)) return rc;       // (the diagonal blocks' row-major copies: once per call)
-        sf::launch_dev_unpack(p->d_xm, pout, n, cw, dX + j0 * ldx, ldx, st);
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        if (sweeps) {
-            if (int rc = sf_solve_finish(p, st)) return rc;
-        } else {
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        float ms = 0;
-        if (elapsed_ms(&ms, e0, e1)) *total_ms += ms;
-    }
-    return SF_OK;
+    *total_ms = t.total_ms;
+    return rc;
 }
 
 int solve_device(sf_chol_plan* p, bool lu, int op, int flags, sf_long nrhs, const sf_float* dB, sf_long ldb, sf_float* dX, sf_long ldx) {
@@ -257,12 +169,12 @@ int solve_device(sf_chol_plan* p, bool lu, int op, int flags, sf_long nrhs, cons
     const sf_long ldmin = std::max<sf_long>(p->n, 1);
     if (ldb < ldmin || ldx < ldmin) return SF_ERR_ARG;
     if ((const void*)dX == (const void*)dB && ldx != ldb) return SF_ERR_ARG;
-    if (dio_refused(p)) return SF_ERR_ARG;
+    if (!sf_plan_whole_resident(p)) return SF_ERR_ARG;
     if (flags && !p->d_perm) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     if (!sf_factor_usable(p)) return SF_ERR_ARG;
     if (nrhs == 0 || p->n <= 0) return SF_OK;
-    if (!dio_device_ptr(p, dB, dio_span(p->n, nrhs, ldb)) || !dio_device_ptr(p, dX, dio_span(p->n, nrhs, ldx))) return SF_ERR_ARG;
+    if (!sf_device_ptr_ok(p, dB, sf_block_span(p->n, nrhs, ldb)) || !sf_device_ptr_ok(p, dX, sf_block_span(p->n, nrhs, ldx))) return SF_ERR_ARG;
     double ms = 0;
     if (int rc = dio_run(p, op, (flags & SF_DEV_PERM_IN) ? p->d_perm : nullptr, (flags & SF_DEV_PERM_OUT) ? p->d_perm : nullptr, nrhs, dB, ldb,
                          dX, ldx, &ms))
@@ -279,7 +191,7 @@ int dio_values_done(sf_chol_plan* p) {
     if (p->lu) {
         // max |a_ij| from the device arrays: the scale of the pivot perturbation
         if (!p->d_dio_part)
-            if (int rc = dio_alloc((void**)&p->d_dio_part, 2 * (size_t)sf::DIO_MAXB * sizeof(double))) return rc;
+            if (int rc = sf_device_alloc((void**)&p->d_dio_part, 2 * (size_t)sf::DIO_MAXB * sizeof(double))) return rc;
         std::vector<double> h(2 * sf::DIO_MAXB, 0.0);
         int nb[2] = {0, 0};
         const double* src[2] = {p->d_Lx, p->u_alias ? nullptr : p->d_Ux};
@@ -309,10 +221,10 @@ int set_values_device(sf_chol_plan* p, bool lu, const sf_float* dLx, const sf_fl
     if (!p || p->lu != lu || (!dLx && p->nnz > 0)) return SF_ERR_ARG;
     const bool need_u = lu && !p->u_alias && p->unz > 0;
     if (need_u && !dUx) return SF_ERR_ARG;
-    if (dio_refused(p)) return SF_ERR_ARG;
+    if (!sf_plan_whole_resident(p)) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
-    if (p->nnz > 0 && !dio_device_ptr(p, dLx, (size_t)p->nnz)) return SF_ERR_ARG;
-    if (need_u && !dio_device_ptr(p, dUx, (size_t)p->unz)) return SF_ERR_ARG;
+    if (p->nnz > 0 && !sf_device_ptr_ok(p, dLx, (size_t)p->nnz)) return SF_ERR_ARG;
+    if (need_u && !sf_device_ptr_ok(p, dUx, (size_t)p->unz)) return SF_ERR_ARG;
     if (p->nnz > 0) HIP_TRY(hipMemcpyAsync(p->d_Lx, dLx, p->nnz * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
     if (need_u) HIP_TRY(hipMemcpyAsync(p->d_Ux, dUx, p->unz * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
     return dio_values_done(p);
@@ -326,9 +238,6 @@ bool dio_map_ok(const sf_long* map, int64_t count, sf_long nsrc) {
 }
 
 }  // namespace
-
-bool sf_device_ptr_ok(const sf_chol_plan* p, const void* ptr, size_t doubles) { return dio_device_ptr(p, ptr, doubles); }
-int sf_solve_many_block(sf_chol_plan* p) { return dio_block(p); }
 
 extern "C" {
 
@@ -348,11 +257,11 @@ int sf_chol_plan_set_ordering(sf_chol_plan* p, const sf_long* perm) {
     } else {
         for (int64_t i = 0; i < n; ++i) h[i] = (int32_t)i;
     }
-    if (dio_refused(p)) return SF_ERR_ARG;
+    if (!sf_plan_whole_resident(p)) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     const size_t bytes = h.size() * sizeof(int32_t);
     if (!p->d_perm) {
-        if (int rc = dio_alloc((void**)&p->d_perm, bytes)) return rc;
+        if (int rc = sf_device_alloc((void**)&p->d_perm, bytes)) return rc;
         p->bytes_ordering += bytes;
     }
     HIP_TRY(hipStreamSynchronize(p->stream));       // (nothing of an earlier call still reads the old ordering)
@@ -373,10 +282,10 @@ int sf_chol_plan_permute_device(sf_chol_plan* p, int inverse, sf_long nrhs, cons
     const sf_long ldmin = std::max<sf_long>(p->n, 1);
     if (ldb < ldmin || ldx < ldmin) return SF_ERR_ARG;
     if ((const void*)dX == (const void*)dB) return SF_ERR_ARG;      // not in place: a permutation has no chunk-local form
-    if (dio_refused(p) || !p->d_perm) return SF_ERR_ARG;
+    if (!sf_plan_whole_resident(p) || !p->d_perm) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     if (nrhs == 0 || p->n <= 0) return SF_OK;
-    if (!dio_device_ptr(p, dB, dio_span(p->n, nrhs, ldb)) || !dio_device_ptr(p, dX, dio_span(p->n, nrhs, ldx))) return SF_ERR_ARG;
+    if (!sf_device_ptr_ok(p, dB, sf_block_span(p->n, nrhs, ldb)) || !sf_device_ptr_ok(p, dX, sf_block_span(p->n, nrhs, ldx))) return SF_ERR_ARG;
     double ms = 0;
     return dio_run(p, DIO_PERMUTE, inverse ? nullptr : p->d_perm, inverse ? p->d_perm : nullptr, nrhs, dB, ldb, dX, ldx, &ms);
 }
@@ -388,32 +297,22 @@ int sf_chol_plan_sample_device(sf_chol_plan* p, sf_long nsamples, uint64_t seed,
     if (!p || !dX || nsamples < 0) return SF_ERR_ARG;
     if (flags & ~SF_DEV_PERM_OUT) return SF_ERR_ARG;
     if (ldx < std::max<sf_long>(p->n, 1)) return SF_ERR_ARG;
-    if (p->lu || dio_refused(p)) return SF_ERR_ARG;
+    if (p->lu || !sf_plan_whole_resident(p)) return SF_ERR_ARG;
     if (flags && !p->d_perm) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     if (!sf_factor_usable(p)) return SF_ERR_ARG;
     if (nsamples == 0 || p->n <= 0) return SF_OK;
-    if (!dio_device_ptr(p, dX, dio_span(p->n, nsamples, ldx))) return SF_ERR_ARG;
-    if (int rc = dio_block(p)) return rc;
-    hipStream_t st = p->stream;
-    const int64_t n = p->n;
+    if (!sf_device_ptr_ok(p, dX, sf_block_span(p->n, nsamples, ldx))) return SF_ERR_ARG;
+    if (int rc = sf_solve_many_block(p)) return rc;
     const int W = sf::SVM_W;
-    const int32_t* pout = flags ? p->d_perm : nullptr;
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    double total_ms = 0;
-    for (sf_long j0 = 0; j0 < nsamples; j0 += W) {
-        const int cw = (int)std::min<sf_long>(W, nsamples - j0);
-        HIP_TRY(hipEventRecord(e0, st));
-        sf::launch_sample_fill(p->d_xm, n, cw, seed, first_sample + (uint64_t)j0, st);
-        if (int rc = dio_sweeps(p, SF_OP_HALF_LT, p->d_xm, W, j0 == 0, st)) return rc;
-        sf::launch_dev_unpack(p->d_xm, pout, n, cw, dX + j0 * ldx, ldx, st);
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        float ms = 0;
-        if (elapsed_ms(&ms, e0, e1)) total_ms += ms;
-    }
-    p->last_sample_ms = total_ms;
+    const SfCols dst{dX, ldx, true, flags ? p->d_perm : nullptr};
+    SfStretch t{p};
+    if (int rc = sf_apply_chunks(p, SfApply{nullptr, &dst, nsamples, W, p->d_xm, 0, true}, t, [&](double* x, sf_long j0, int cw) {
+            sf::launch_sample_fill(x, p->n, cw, seed, first_sample + (uint64_t)j0, p->stream);
+            return sf_apply_sweep(p, SF_SWEEP_BWD, x, W, j0 == 0);
+        }))
+        return rc;
+    p->last_sample_ms = t.total_ms;
     return SF_OK;
 }
 
@@ -425,13 +324,13 @@ int sf_chol_plan_set_value_map(sf_chol_plan* p, sf_long nsrc, const sf_long* map
     const bool need_u = p->lu && !p->u_alias && p->unz > 0;
     if (need_u && !mapU) return SF_ERR_ARG;
     if (!dio_map_ok(mapL, p->nnz, nsrc) || (need_u && !dio_map_ok(mapU, p->unz, nsrc))) return SF_ERR_ARG;
-    if (dio_refused(p)) return SF_ERR_ARG;
+    if (!sf_plan_whole_resident(p)) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipStreamSynchronize(p->stream));
     const size_t nl = (size_t)std::max<int64_t>(p->nnz, 1), nu = need_u ? (size_t)p->unz : 0;
     if (!p->d_vmap) {
         const size_t bytes = (nl + nu) * sizeof(int64_t);
-        if (int rc = dio_alloc((void**)&p->d_vmap, bytes)) return rc;
+        if (int rc = sf_device_alloc((void**)&p->d_vmap, bytes)) return rc;
         p->bytes_ordering += bytes;
     }
     if (p->nnz > 0) HIP_TRY(hipMemcpy(p->d_vmap, mapL, (size_t)p->nnz * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -445,9 +344,9 @@ int sf_lu_plan_set_value_map(sf_lu_plan* p, sf_long nsrc, const sf_long* mapL, c
 
 int sf_chol_plan_set_values_mapped_device(sf_chol_plan* p, const sf_float* dAx) {
     if (!p || !dAx) return SF_ERR_ARG;
-    if (dio_refused(p) || !p->d_vmap) return SF_ERR_ARG;
+    if (!sf_plan_whole_resident(p) || !p->d_vmap) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
-    if (p->vmap_nsrc > 0 && !dio_device_ptr(p, dAx, (size_t)p->vmap_nsrc)) return SF_ERR_ARG;
+    if (p->vmap_nsrc > 0 && !sf_device_ptr_ok(p, dAx, (size_t)p->vmap_nsrc)) return SF_ERR_ARG;
     hipStream_t st = p->stream;
     const bool need_u = p->lu && !p->u_alias && p->unz > 0;
     const size_t nl = (size_t)std::max<int64_t>(p->nnz, 1);

@@ -89,11 +89,6 @@ void launch_gram_row(const double* Y, int64_t n, int a, int64_t k, double* part,
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
-// the plans sf_chol_plan_quadform runs on: whole, resident Cholesky plans
-bool gram_refused(const sf_chol_plan* p) {
-    return p->dry || p->lu || p->partial || p->nranks > 1 || p->ooc_groups > 1 || (p->nsuper > 0 && !p->d_solve);
-}
-
 // doubles of the store for nch chunks: the Y blocks | the parts of one chunk row | the (16 nch)^2 result of the host-array call
 struct GramLayout { size_t y, part, g; };
 GramLayout gram_layout(int64_t n, int64_t nch) {
@@ -119,41 +114,30 @@ int gram_store(sf_chol_plan* p, int64_t nch) {
     return SF_OK;
 }
 
-// the forward half on x (the sync block is cleared here)
-int gram_sweep(sf_chol_plan* p, double* x, int width, hipStream_t st) {
-    const SolveSync y = sf_solve_sync(p);
-    HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, y.bytes, st));
-    for (size_t k = 0; k < p->solve_steps.size(); ++k) sf_solve_step_fwd(p, k, p->d_Lsx, x, width, y, st);
-    return SF_OK;
-}
-
-void gram_add_ms(sf_chol_plan* p, double* total) {
-    float ms = 0;
-    if (elapsed_ms(&ms, p->ev_s0, p->ev_s1)) *total += ms;
-}
-
 // B (host, dev == false; device otherwise, pin = the ordering for the way in or null) -> G.  Host: G is the caller's array, filled
 // from the store's result block; device: the final kernel writes the caller's dG itself.
 int gram_run(sf_chol_plan* p, bool dev, const int32_t* pin, sf_long k, const double* B, sf_long ldb, double* G, sf_long ldg) {
     hipStream_t st = p->stream;
     const int64_t n = p->n;
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    double total_ms = 0;
+    const SfCols src{const_cast<double*>(B), ldb, dev, pin};
+    SfStretch t{p};
     if (k == 1) {
         // the one-column family on d_x and quadform's reduction
         if (int rc = sf_quadform_scratch(p)) return rc;
         const double* d_q = p->d_qf + (size_t)sf::QF_MAXB;
-        if (!dev) HIP_TRY(hipMemcpyAsync(p->d_x, B, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(e0, st));
-        if (dev) sf::launch_dev_load1(B, pin, n, p->d_x, st);
-        if (int rc = gram_sweep(p, p->d_x, 1, st)) return rc;
-        sf::launch_quadform(p->d_x, n, 1, p->d_qf, st);
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(G, d_q, sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        gram_add_ms(p, &total_ms);
-        p->last_gram_ms = total_ms;
+        if (int rc = sf_apply_chunks(
+                p, SfApply{&src, nullptr, 1, 1, p->d_x, 0, true}, t,
+                [&](double* x, sf_long, int) {
+                    if (int rc = sf_apply_sweep(p, SF_SWEEP_FWD_L, x, 1, false)) return rc;
+                    sf::launch_quadform(x, n, 1, p->d_qf, st);
+                    return SF_OK;
+                },
+                [&](double*, sf_long, int) {
+                    HIP_TRY(hipMemcpyAsync(G, d_q, sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+                    return SF_OK;
+                }))
+            return rc;
+        p->last_gram_ms = t.total_ms;
         p->last_gram_parts = 0;
         return SF_OK;
     }
@@ -167,30 +151,13 @@ int gram_run(sf_chol_plan* p, bool dev, const int32_t* pin, sf_long k, const dou
     double* part = Y + L.y;
     double* Gd = dev ? G : part + L.part;
     const int64_t ldgd = dev ? ldg : k;
-    double* stage = dev ? nullptr : p->d_xm + (size_t)n * W;
-    for (int64_t c = 0; c < nch; ++c) {
-        const sf_long j0 = c * W;
-        const int cw = (int)std::min<sf_long>(W, k - j0);
-        double* Yc = Y + (size_t)c * n * W;
-        if (!dev) {
-            if (n == ldb) {
-                HIP_TRY(hipMemcpyAsync(stage, B + j0 * ldb, (size_t)n * cw * sizeof(double), hipMemcpyHostToDevice, st));
-            } else {
-                HIP_TRY(hipMemcpy2DAsync(stage, (size_t)n * sizeof(double), B + j0 * ldb, (size_t)ldb * sizeof(double), (size_t)n * sizeof(double),
-                                         cw, hipMemcpyHostToDevice, st));
-            }
-        }
-        HIP_TRY(hipEventRecord(e0, st));
-        // (both packs write zeros into the columns [cw, W) of the block: the padding of the last chunk)
-        if (dev) sf::launch_dev_pack(B + j0 * ldb, ldb, pin, n, cw, Yc, st);
-        else sf::launch_solve_many_pack(stage, n, cw, Yc, st);
-        if (int rc = gram_sweep(p, Yc, W, st)) return rc;
-        sf::launch_gram_row(Y, n, (int)c, k, part, Gd, ldgd, st);
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        gram_add_ms(p, &total_ms);
-    }
+    // chunk c into its own block of the store, its row of G as soon as it has been swept
+    if (int rc = sf_apply_chunks(p, SfApply{&src, nullptr, k, W, Y, (size_t)n * W, true}, t, [&](double* Yc, sf_long j0, int) {
+            if (int rc = sf_apply_sweep(p, SF_SWEEP_FWD_L, Yc, W, false)) return rc;
+            sf::launch_gram_row(Y, n, (int)(j0 / W), k, part, Gd, ldgd, st);
+            return SF_OK;
+        }))
+        return rc;
     if (!dev) {
         HIP_TRY(hipMemcpy2DAsync(G, (size_t)ldg * sizeof(double), Gd, (size_t)k * sizeof(double), (size_t)k * sizeof(double), k,
                                  hipMemcpyDeviceToHost, st));
@@ -198,7 +165,7 @@ int gram_run(sf_chol_plan* p, bool dev, const int32_t* pin, sf_long k, const dou
     }
     int64_t slab_rows = 0;
     p->last_gram_parts = sf::gram_slabs(n, &slab_rows);
-    p->last_gram_ms = total_ms;
+    p->last_gram_ms = t.total_ms;
     return SF_OK;
 }
 
@@ -206,7 +173,7 @@ int gram_run(sf_chol_plan* p, bool dev, const int32_t* pin, sf_long k, const dou
 int gram_args(sf_chol_plan* p, sf_long k, sf_long ldb, sf_long ldg) {
     if (k < 0 || k > SF_GRAM_MAX_K) return SF_ERR_ARG;
     if (ldb < std::max<sf_long>(p->n, 1) || ldg < std::max<sf_long>(k, 1)) return SF_ERR_ARG;
-    if (gram_refused(p)) return SF_ERR_ARG;
+    if (p->lu || !sf_plan_whole_resident(p)) return SF_ERR_ARG;
     return SF_OK;
 }
 
@@ -236,11 +203,9 @@ int sf_chol_plan_gram_device(sf_chol_plan* p, int flags, sf_long k, const sf_flo
     HIP_TRY(hipSetDevice(p->device));
     if (!sf_factor_usable(p)) return SF_ERR_ARG;
     if (k == 0) return SF_OK;
-    const size_t span_b = p->n > 0 ? (size_t)(k - 1) * (size_t)ldb + (size_t)p->n : 0;
-    const size_t span_g = (size_t)(k - 1) * (size_t)ldg + (size_t)k;
+    const size_t span_b = sf_block_span(p->n, k, ldb), span_g = sf_block_span(k, k, ldg);
     if ((span_b && !sf_device_ptr_ok(p, dB, span_b)) || !sf_device_ptr_ok(p, dG, span_g)) return SF_ERR_ARG;
-    const uintptr_t b0 = (uintptr_t)dB, g0 = (uintptr_t)dG;
-    if (b0 < g0 + span_g * sizeof(double) && g0 < b0 + span_b * sizeof(double)) return SF_ERR_ARG;      // the result overlaps the block
+    if (sf_blocks_overlap(dG, span_g, dB, span_b)) return SF_ERR_ARG;      // the result overlaps the block
     if (p->n <= 0) {
         HIP_TRY(hipMemset2DAsync(dG, (size_t)ldg * sizeof(double), 0, (size_t)k * sizeof(double), k, p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));

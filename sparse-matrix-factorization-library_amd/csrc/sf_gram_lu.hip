@@ -114,52 +114,6 @@ void launch_dot(const double* x, const double* y, int64_t n, double* scratch, do
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
-// the plans these entry points run on: whole, resident LU plans
-bool lug_refused(const sf_chol_plan* p) {
-    return p->dry || !p->lu || p->partial || p->nranks > 1 || p->ooc_groups > 1 || (p->nsuper > 0 && !p->d_solve);
-}
-
-// one half on x (the sync block is cleared here).  copies: the backward halves make their row-major diagonal copies, U from the
-// U^T panels and LT from the L panels -- neither may see the other's (sf_solve_t.hip)
-int lug_sweep(sf_chol_plan* p, int which, double* x, int width, bool copies, hipStream_t st) {
-    const SolveSync y = sf_solve_sync(p);
-    HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, y.bytes, st));
-    switch (which) {
-        case SF_LU_HALF_L:
-            for (size_t k = 0; k < p->solve_steps.size(); ++k) sf_solve_step_fwd(p, k, p->d_Lsx, x, width, y, st);
-            break;
-        case SF_LU_HALF_U: sf_solve_sweep_bwd(p, x, width, copies, y, st); break;
-        case SF_LU_HALF_UT: tsolve_sweep_fwd(p, x, width, y, st); break;
-        default: tsolve_sweep_bwd(p, x, width, copies, y, st); break;
-    }
-    return SF_OK;
-}
-
-void lug_add_ms(sf_chol_plan* p, double* total) {
-    float ms = 0;
-    if (elapsed_ms(&ms, p->ev_s0, p->ev_s1)) *total += ms;
-}
-
-// a chunk of cw columns between the host (column-major, leading dimension ld) and the staging half
-int lug_stage_in(const double* B, sf_long ld, int64_t n, int cw, double* stage, hipStream_t st) {
-    if (ld == n) {
-        HIP_TRY(hipMemcpyAsync(stage, B, (size_t)n * cw * sizeof(double), hipMemcpyHostToDevice, st));
-    } else {
-        for (int c = 0; c < cw; ++c)
-            HIP_TRY(hipMemcpyAsync(stage + (size_t)c * n, B + (size_t)c * ld, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    return SF_OK;
-}
-int lug_stage_out(double* X, sf_long ld, int64_t n, int cw, const double* stage, hipStream_t st) {
-    if (ld == n) {
-        HIP_TRY(hipMemcpyAsync(X, stage, (size_t)n * cw * sizeof(double), hipMemcpyDeviceToHost, st));
-    } else {
-        for (int c = 0; c < cw; ++c)
-            HIP_TRY(hipMemcpyAsync(X + (size_t)c * ld, stage + (size_t)c * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    return SF_OK;
-}
-
 // doubles of the store for nz chunks of C and ny chunks of B: the Z blocks | the Y blocks | the parts of one chunk column | the
 // padded (16 nz) x (16 ny) result of the host-array call
 struct Gram2Layout { size_t z, y, part, g; };
@@ -197,9 +151,9 @@ int lug_run(sf_chol_plan* p, bool dev, const int32_t* pin, sf_long m, const doub
             double* G, sf_long ldg) {
     hipStream_t st = p->stream;
     const int64_t n = p->n;
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    double total_ms = 0;
     const int W = sf::SVM_W;
+    const SfCols srcC{const_cast<double*>(C), ldc, dev, pin}, srcB{const_cast<double*>(B), ldb, dev, pin};
+    SfStretch t{p};
     if (!dev || (m == 1 && k == 1))
         if (int rc = sf_solve_many_block(p)) return rc;     // (its staging half takes the chunks of a host block; one column: z)
     if (m == 1 && k == 1) {
@@ -207,27 +161,22 @@ int lug_run(sf_chol_plan* p, bool dev, const int32_t* pin, sf_long m, const doub
         if (int rc = sf_quadform_scratch(p)) return rc;
         double* z = p->d_xm;
         double* d_out = p->d_qf + (size_t)sf::QF_MAXB;
-        if (!dev) {
-            HIP_TRY(hipMemcpyAsync(z, C, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(p->d_x, B, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-        }
-        HIP_TRY(hipEventRecord(e0, st));
-        if (dev) sf::launch_dev_load1(C, pin, n, z, st);
-        if (int rc = lug_sweep(p, SF_LU_HALF_UT, z, 1, false, st)) return rc;
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        lug_add_ms(p, &total_ms);
-        HIP_TRY(hipEventRecord(e0, st));
-        if (dev) sf::launch_dev_load1(B, pin, n, p->d_x, st);
-        if (int rc = lug_sweep(p, SF_LU_HALF_L, p->d_x, 1, false, st)) return rc;
+        // spelled out with the driver's pieces: both columns are staged before the first of the two stretches
+        if (int rc = sf_cols_stage_in(p, srcC, 0, 1, z)) return rc;
+        if (int rc = sf_cols_stage_in(p, srcB, 0, 1, p->d_x)) return rc;
+        if (int rc = t.open()) return rc;
+        sf_cols_load(p, srcC, 0, 1, 1, z, z);
+        if (int rc = sf_apply_sweep(p, SF_SWEEP_FWD_UT, z, 1, false)) return rc;
+        if (int rc = t.mark()) return rc;
+        if (int rc = t.close(true)) return rc;
+        if (int rc = t.open()) return rc;
+        sf_cols_load(p, srcB, 0, 1, 1, p->d_x, p->d_x);
+        if (int rc = sf_apply_sweep(p, SF_SWEEP_FWD_L, p->d_x, 1, false)) return rc;
         sf::launch_dot(z, p->d_x, n, p->d_qf, d_out, st);
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
+        if (int rc = t.mark()) return rc;
         HIP_TRY(hipMemcpyAsync(G, d_out, sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        lug_add_ms(p, &total_ms);
-        p->last_gram_ms = total_ms;
+        if (int rc = t.close(true)) return rc;
+        p->last_gram_ms = t.total_ms;
         p->last_gram_parts = 0;
         return SF_OK;
     }
@@ -239,35 +188,16 @@ int lug_run(sf_chol_plan* p, bool dev, const int32_t* pin, sf_long m, const doub
     double* part = Y + L.y;
     double* Gd = dev ? G : part + L.part;
     const int64_t ldgd = dev ? ldg : m;
-    double* stage = dev ? nullptr : p->d_xm + (size_t)n * W;
-    // one chunk: into its block (both packs write zeros into the columns [cw, W): the padding of a last chunk), then its sweep
-    auto chunk = [&](const double* S, sf_long lds, sf_long j0, int cw, int which, double* blk) -> int {
-        if (!dev)
-            if (int rc = lug_stage_in(S + j0 * lds, lds, n, cw, stage, st)) return rc;
-        HIP_TRY(hipEventRecord(e0, st));
-        if (dev) sf::launch_dev_pack(S + j0 * lds, lds, pin, n, cw, blk, st);
-        else sf::launch_solve_many_pack(stage, n, cw, blk, st);
-        return lug_sweep(p, which, blk, W, false, st);
-    };
-    auto chunk_end = [&]() -> int {
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        lug_add_ms(p, &total_ms);
-        return SF_OK;
-    };
-    for (int64_t a = 0; a < nz; ++a) {
-        const sf_long j0 = a * W;
-        if (int rc = chunk(C, ldc, j0, (int)std::min<sf_long>(W, m - j0), SF_LU_HALF_UT, Z + (size_t)a * n * W)) return rc;
-        if (int rc = chunk_end()) return rc;
-    }
-    for (int64_t b = 0; b < ny; ++b) {
-        const sf_long j0 = b * W;
-        double* Yb = Y + (size_t)b * n * W;
-        if (int rc = chunk(B, ldb, j0, (int)std::min<sf_long>(W, k - j0), SF_LU_HALF_L, Yb)) return rc;
-        sf::launch_gram2_col(Z, Yb, n, (int)nz, (int)b, m, k, part, Gd, ldgd, st);
-        if (int rc = chunk_end()) return rc;
-    }
+    // every chunk into its own block of the store: Z = U^{-T} C first, then Y = F B, column b of G as soon as chunk b has been swept
+    if (int rc = sf_apply_chunks(p, SfApply{&srcC, nullptr, m, W, Z, (size_t)n * W, true}, t,
+                                 [&](double* Za, sf_long, int) { return sf_apply_sweep(p, SF_SWEEP_FWD_UT, Za, W, false); }))
+        return rc;
+    if (int rc = sf_apply_chunks(p, SfApply{&srcB, nullptr, k, W, Y, (size_t)n * W, true}, t, [&](double* Yb, sf_long j0, int) {
+            if (int rc = sf_apply_sweep(p, SF_SWEEP_FWD_L, Yb, W, false)) return rc;
+            sf::launch_gram2_col(Z, Yb, n, (int)nz, (int)(j0 / W), m, k, part, Gd, ldgd, st);
+            return SF_OK;
+        }))
+        return rc;
     if (!dev) {
         HIP_TRY(hipMemcpy2DAsync(G, (size_t)ldg * sizeof(double), Gd, (size_t)m * sizeof(double), (size_t)m * sizeof(double), k,
                                  hipMemcpyDeviceToHost, st));
@@ -275,7 +205,7 @@ int lug_run(sf_chol_plan* p, bool dev, const int32_t* pin, sf_long m, const doub
     }
     int64_t slab_rows = 0;
     p->last_gram_parts = sf::gram_slabs(n, &slab_rows);
-    p->last_gram_ms = total_ms;
+    p->last_gram_ms = t.total_ms;
     return SF_OK;
 }
 
@@ -284,16 +214,8 @@ int lug_args(sf_chol_plan* p, sf_long m, sf_long ldc, sf_long k, sf_long ldb, sf
     if (m < 0 || m > SF_GRAM_MAX_K || k < 0 || k > SF_GRAM_MAX_K) return SF_ERR_ARG;
     const sf_long ldmin = std::max<sf_long>(p->n, 1);
     if (ldc < ldmin || ldb < ldmin || ldg < std::max<sf_long>(m, 1)) return SF_ERR_ARG;
-    if (lug_refused(p)) return SF_ERR_ARG;
+    if (!p->lu || !sf_plan_whole_resident(p)) return SF_ERR_ARG;
     return SF_OK;
-}
-
-// doubles a column-major block of `cols` columns of `rows` rows spans
-size_t lug_span(int64_t rows, sf_long cols, sf_long ld) { return (rows > 0 && cols > 0) ? (size_t)(cols - 1) * (size_t)ld + (size_t)rows : 0; }
-
-bool lug_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return na && nb && a0 < b0 + nb * sizeof(double) && b0 < a0 + na * sizeof(double);
 }
 
 }  // namespace
@@ -306,44 +228,21 @@ int sf_lu_plan_solve_half(sf_lu_plan* p, int which, sf_long nrhs, const sf_float
     const sf_long ldmin = std::max<sf_long>(p->n, 1);
     if (ldb < ldmin || ldx < ldmin) return SF_ERR_ARG;
     if ((const void*)X == (const void*)B && ldx != ldb) return SF_ERR_ARG;
-    if (lug_refused(p)) return SF_ERR_ARG;
+    if (!p->lu || !sf_plan_whole_resident(p)) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     if (!sf_factor_usable(p)) return SF_ERR_ARG;
     if (nrhs == 0 || p->n <= 0) return SF_OK;
-    hipStream_t st = p->stream;
-    const int64_t n = p->n;
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    double total_ms = 0;
-    if (nrhs == 1) {
-        // the one-column family on d_x
-        HIP_TRY(hipMemcpyAsync(p->d_x, B, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(e0, st));
-        if (int rc = lug_sweep(p, which, p->d_x, 1, true, st)) return rc;
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(X, p->d_x, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        lug_add_ms(p, &total_ms);
-        p->last_half_ms = total_ms;
-        return SF_OK;
-    }
-    if (int rc = sf_solve_many_block(p)) return rc;
-    const int W = sf::SVM_W;
-    double* stage = p->d_xm + (size_t)n * W;
-    for (sf_long j0 = 0; j0 < nrhs; j0 += W) {
-        const int cw = (int)std::min<sf_long>(W, nrhs - j0);
-        if (int rc = lug_stage_in(B + j0 * ldb, ldb, n, cw, stage, st)) return rc;
-        HIP_TRY(hipEventRecord(e0, st));
-        sf::launch_solve_many_pack(stage, n, cw, p->d_xm, st);
-        if (int rc = lug_sweep(p, which, p->d_xm, W, j0 == 0, st)) return rc;     // (a backward half's diagonal copies: the first chunk of EVERY call)
-        sf::launch_solve_many_unpack(p->d_xm, n, cw, stage, st);
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        if (int rc = lug_stage_out(X + j0 * ldx, ldx, n, cw, stage, st)) return rc;
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        lug_add_ms(p, &total_ms);
-    }
-    p->last_half_ms = total_ms;
+    const int W = nrhs == 1 ? 1 : sf::SVM_W;        // (one column: the one-column family on d_x)
+    if (W > 1)
+        if (int rc = sf_solve_many_block(p)) return rc;
+    const SfSweep op = which == SF_LU_HALF_L ? SF_SWEEP_FWD_L : which == SF_LU_HALF_U ? SF_SWEEP_BWD : which == SF_LU_HALF_UT ? SF_SWEEP_FWD_UT : SF_SWEEP_BWD_LT;
+    const SfCols src{const_cast<double*>(B), ldb, false, nullptr}, dst{X, ldx, false, nullptr};
+    SfStretch t{p};
+    // (a backward half's diagonal copies: the first chunk of EVERY call)
+    if (int rc = sf_apply_chunks(p, SfApply{&src, &dst, nrhs, W, W == 1 ? p->d_x : p->d_xm, 0, true}, t,
+                                 [&](double* x, sf_long j0, int) { return sf_apply_sweep(p, op, x, W, j0 == 0); }))
+        return rc;
+    p->last_half_ms = t.total_ms;
     return SF_OK;
 }
 
@@ -371,10 +270,11 @@ int sf_lu_plan_gram_device(sf_lu_plan* p, int flags, sf_long m, const sf_float* 
     HIP_TRY(hipSetDevice(p->device));
     if (!sf_factor_usable(p)) return SF_ERR_ARG;
     if (m == 0 || k == 0) return SF_OK;
-    const size_t span_c = lug_span(p->n, m, ldc), span_b = lug_span(p->n, k, ldb), span_g = lug_span(m, k, ldg);
+    const size_t span_c = sf_block_span(p->n, m, ldc), span_b = sf_block_span(p->n, k, ldb), span_g = sf_block_span(m, k, ldg);
     if ((span_c && !sf_device_ptr_ok(p, dC, span_c)) || (span_b && !sf_device_ptr_ok(p, dB, span_b)) || !sf_device_ptr_ok(p, dG, span_g))
         return SF_ERR_ARG;
-    if (lug_overlap(dG, span_g, dC, span_c) || lug_overlap(dG, span_g, dB, span_b)) return SF_ERR_ARG;      // the result overlaps an input
+    // the result overlaps an input (n == 0: there are none)
+    if (p->n > 0 && (sf_blocks_overlap(dG, span_g, dC, span_c) || sf_blocks_overlap(dG, span_g, dB, span_b))) return SF_ERR_ARG;
     if (p->n <= 0) {
         HIP_TRY(hipMemset2DAsync(dG, (size_t)ldg * sizeof(double), 0, (size_t)m * sizeof(double), k, p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));

@@ -226,11 +226,15 @@ void launch_sample_fill(double* X, int64_t n, int cw, uint64_t seed, uint64_t s0
 constexpr int QF_MAXB = 1024;
 void launch_quadform(const double* X, int64_t n, int width, double* scratch, hipStream_t st);
 
-// ---- device-pointer loads (sf_device_io.hip), shared with sf_gram.hip: perm != nullptr gathers row perm[i] of the caller's block ----
-// x[i] = B[perm ? perm[i] : i]
+// ---- device-pointer loads and stores (sf_device_io.hip; called by sf_apply.hip): perm != nullptr gathers / scatters row perm[i] of
+// the caller's block ----
+// x[i] = B[perm ? perm[i] : i], and X[perm ? perm[i] : i] = x[i]
 void launch_dev_load1(const double* B, const int32_t* perm, int64_t n, double* x, hipStream_t st);
+void launch_dev_store1(const double* x, const int32_t* perm, int64_t n, double* X, hipStream_t st);
 // the caller's column-major chunk of cw <= SVM_W columns -> the row-major n x SVM_W block X, columns [cw, SVM_W) zero
 void launch_dev_pack(const double* B, int64_t ldb, const int32_t* perm, int64_t n, int cw, double* X, hipStream_t st);
+// and back: the columns [0, cw) of the block into the caller's chunk D
+void launch_dev_unpack(const double* X, const int32_t* perm, int64_t n, int cw, double* D, int64_t ldx, hipStream_t st);
 
 // ---- the Gram matrix Y^T Y of the chunks of a half-solved border (sf_gram.hip, sf_chol_plan_gram) ----
 constexpr int GRAM_SLAB_ROWS = 2048;    // rows of a slab, about

@@ -150,13 +150,60 @@ void tsolve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, h
 // diagonal copies, made from the L panels)
 void tsolve_sweep_fwd(sf_chol_plan* p, double* x, int width, const SolveSync& y, hipStream_t st);
 void tsolve_sweep_bwd(sf_chol_plan* p, double* x, int width, bool transpose_diag, const SolveSync& y, hipStream_t st);
-// ---- shared with the Gram matrix (sf_gram.hip) ----
-// `ptr` is device (or managed) memory of the plan's device with room for `doubles` doubles from there on (sf_device_io.hip)
+// ---- the host protocol of every entry point that takes columns through the resident factor (sf_apply.hip) ----
+// the plan is whole and resident: one rank's, in core, with the solve's task lists
+bool sf_plan_whole_resident(const sf_chol_plan* p);
+// `ptr` is device (or managed) memory of the plan's device with room for `doubles` doubles from there on
 bool sf_device_ptr_ok(const sf_chol_plan* p, const void* ptr, size_t doubles);
-// the n x SVM_W block d_xm with its staging half, allocated by whichever call comes first (sf_device_io.hip)
+// doubles a column-major block of `cols` columns of `rows` rows spans; two such ranges of device memory share a byte (an empty one:
+// it starts strictly inside the other)
+size_t sf_block_span(int64_t rows, sf_long cols, sf_long ld);
+bool sf_blocks_overlap(const void* a, size_t na, const void* b, size_t nb);
+// an allocation that is kept; a failure is SF_ERR_ALLOC, leaves *ptr null and no error behind in the runtime
+int sf_device_alloc(void** ptr, size_t bytes);
+// the n x SVM_W block d_xm with its staging half / the parts and results of launch_quadform, d_qf: allocated by whichever call
+// needs them first
 int sf_solve_many_block(sf_chol_plan* p);
-// the parts and results of launch_quadform, d_qf, allocated by the first call that needs them (sf_sample.hip)
 int sf_quadform_scratch(sf_chol_plan* p);
+// One operator on x (width 1: x[n]; sf::SVM_W: a row-major block) on the plan's stream, the sync block cleared first.  SOLVE and
+// TRANS are both sweeps of A^{-1} and (LU) A^{-T}; FWD_L the forward steps over the L panels; BWD sf_solve_sweep_bwd (L^{-T}, LU:
+// U^{-1}); FWD_UT and BWD_LT the halves of TRANS.  copies: the backward sweep first makes its row-major diagonal copies.
+enum SfSweep { SF_SWEEP_SOLVE, SF_SWEEP_TRANS, SF_SWEEP_FWD_L, SF_SWEEP_BWD, SF_SWEEP_FWD_UT, SF_SWEEP_BWD_LT };
+int sf_apply_sweep(sf_chol_plan* p, SfSweep op, double* x, int width, bool copies);
+// The timed stretch between the plan's solve events: open() records ev_s0; mark() records ev_s1 and polls the runtime's last
+// error; close() waits for the stream -- through sf_solve_finish when sweeps ran, so that the info word is read -- and adds the
+// stretch to total_ms (where the events' time can be read).  Copies enqueued between mark() and close() are waited for and not timed.
+struct SfStretch {
+    sf_chol_plan* p;
+    double total_ms = 0;
+    bool timed = false;     // some stretch's time could be read
+    int open();
+    int mark();
+    int close(bool sweeps);
+};
+// A column-major block of the caller's, in host memory or (dev) in device memory, there optionally in the caller's ordering
+struct SfCols { double* ptr; sf_long ld; bool dev; const int32_t* perm; };
+// The two phases of a chunk of cw columns from column j0 on.  stage_in / stage_out: a host block to / from `stage` (column-major,
+// leading dimension n), outside the timed stretch; a device block: nothing.  load / store: `stage` or the device block to / from
+// x, inside it; width 1 works on x where it is staged (stage == x).
+int sf_cols_stage_in(sf_chol_plan* p, const SfCols& s, sf_long j0, int cw, double* stage);
+void sf_cols_load(sf_chol_plan* p, const SfCols& s, sf_long j0, int cw, int width, const double* stage, double* x);
+void sf_cols_store(sf_chol_plan* p, const SfCols& d, sf_long j0, int cw, int width, const double* x, double* stage);
+int sf_cols_stage_out(sf_chol_plan* p, const SfCols& d, sf_long j0, int cw, const double* stage);
+// The chunk loop.  For every chunk of at most `width` columns of ncols: stage in, open the stretch, load, body(x, j0, cw), store,
+// mark, tail(x, j0, cw), stage out, close.  src == null: the body makes the columns; dst == null: the body or the tail disposes
+// of them.  width 1 (ncols == 1) is the one-column family on x[n]; width SVM_W works on the row-major block x + chunk * xstride,
+// and a host block then goes through the staging half of d_xm (the caller has called sf_solve_many_block).
+struct SfApply {
+    const SfCols* src;
+    const SfCols* dst;
+    sf_long ncols;
+    int width;
+    double* x;
+    size_t xstride;
+    bool sweeps;        // the body runs sweeps (what close() is told)
+};
+// (the loop itself, a template on its two callables int(double* x, sf_long j0, int cw), follows the plan below)
 
 struct sf_chol_plan {
     // ---- overlapped download schedule (built once) and the state of a running download ----
@@ -391,6 +438,30 @@ struct sf_chol_plan {
     std::vector<int> level_of;
 };
 
+template <class Body, class Tail>
+int sf_apply_chunks(sf_chol_plan* p, const SfApply& a, SfStretch& t, Body&& body, Tail&& tail) {
+    for (sf_long j0 = 0; j0 < a.ncols; j0 += a.width) {
+        const int cw = (int)std::min<sf_long>(a.width, a.ncols - j0);
+        double* x = a.x + (size_t)(j0 / a.width) * a.xstride;
+        double* stage = a.width == 1 ? x : p->d_xm ? p->d_xm + (size_t)p->n * a.width : nullptr;
+        if (a.src)
+            if (int rc = sf_cols_stage_in(p, *a.src, j0, cw, stage)) return rc;
+        if (int rc = t.open()) return rc;
+        if (a.src) sf_cols_load(p, *a.src, j0, cw, a.width, stage, x);
+        if (int rc = body(x, j0, cw)) return rc;
+        if (a.dst) sf_cols_store(p, *a.dst, j0, cw, a.width, x, stage);
+        if (int rc = t.mark()) return rc;
+        if (int rc = tail(x, j0, cw)) return rc;
+        if (a.dst)
+            if (int rc = sf_cols_stage_out(p, *a.dst, j0, cw, stage)) return rc;
+        if (int rc = t.close(a.sweeps)) return rc;
+    }
+    return SF_OK;
+}
+template <class Body>
+int sf_apply_chunks(sf_chol_plan* p, const SfApply& a, SfStretch& t, Body&& body) {
+    return sf_apply_chunks(p, a, t, body, [](double*, sf_long, int) { return SF_OK; });
+}
 
 // Overlapped download (sf_chol_plan.hip).  sf_dl_begin starts the copy workers of a factorization whose launches are
 // about to be enqueued with run_launches (which records and publishes the piece events while dl_active is set);

@@ -378,7 +378,6 @@ int sf_chol_plan_refine(sf_chol_plan* p, const sf_float* b_host, sf_float* x_hos
     hipStream_t st = p->stream;
     const RefineVecs v = refine_vecs(p);
     const size_t nb = (size_t)p->n * sizeof(double);
-    const size_t sync_bytes = sf_solve_sync(p).bytes;
     hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
     double total_ms = 0.0;
     RefineScalars s;
@@ -394,8 +393,7 @@ int sf_chol_plan_refine(sf_chol_plan* p, const sf_float* b_host, sf_float* x_hos
     HIP_TRY(hipMemcpyAsync(v.b, b_host, nb, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(e0, st));
     HIP_TRY(hipMemcpyAsync(v.x, v.b, nb, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, sync_bytes, st));
-    sf_solve_sweeps(p, v.x, 1, true, st);
+    if (int rc = sf_apply_sweep(p, SF_SWEEP_SOLVE, v.x, 1, true)) return rc;
     if (int rc = refine_eval(p, v, v.x, true, st)) return rc;
     if (int rc = finish_step()) return rc;
 
@@ -405,8 +403,7 @@ int sf_chol_plan_refine(sf_chol_plan* p, const sf_float* b_host, sf_float* x_hos
     int k = 0;
     while (std::isfinite(cur) && cur > tol && k < max_iter && !(k >= 1 && cur > 0.5 * prev)) {
         HIP_TRY(hipEventRecord(e0, st));
-        HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, sync_bytes, st));
-        sf_solve_sweeps(p, v.r, 1, false, st);                      // d = solve(r), in place (the factor has not changed: no new transposes)
+        if (int rc = sf_apply_sweep(p, SF_SWEEP_SOLVE, v.r, 1, false)) return rc;      // d = solve(r), in place (the factor has not changed: no new transposes)
         sf::launch_refine_update(p->n, v.x, v.r, v.best, best_in_x ? 1 : 0, st);
         if (int rc = refine_eval(p, v, v.x, true, st)) return rc;
         if (int rc = finish_step()) return rc;

@@ -152,84 +152,18 @@ void launch_quadform(const double* X, int64_t n, int width, double* scratch, hip
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
-// the plans the half solves run on: whole, resident Cholesky plans
-bool half_refused(const sf_chol_plan* p) {
-    return p->dry || p->lu || p->partial || p->nranks > 1 || p->ooc_groups > 1 || (p->nsuper > 0 && !p->d_solve);
-}
-
-// the checks every entry point makes once its own arguments are in order; *go = false: nothing to do (SF_OK)
+// the checks every entry point makes once its own arguments are in order, on whole, resident Cholesky plans; *go = false: nothing
+// to do (SF_OK)
 int half_begin(sf_chol_plan* p, sf_long count, bool* go) {
     *go = false;
-    if (half_refused(p)) return SF_ERR_ARG;
+    if (p->lu || !sf_plan_whole_resident(p)) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     if (!sf_factor_usable(p)) return SF_ERR_ARG;
     *go = count > 0 && p->n > 0;
     return SF_OK;
 }
 
-// an allocation of the first call that is kept; a failure leaves the plan as it was
-int half_alloc(double** ptr, size_t bytes) {
-    if (*ptr) return SF_OK;
-    if (hipMalloc((void**)ptr, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        *ptr = nullptr;
-        return SF_ERR_ALLOC;
-    }
-    return SF_OK;
-}
-
-// the n x SVM_W row-major block and its column-major staging half (sf_chol_plan_solve_many's, whichever call comes first)
-int half_block(sf_chol_plan* p) {
-    const size_t bytes = 2 * (size_t)p->n * sf::SVM_W * sizeof(double);
-    const bool fresh = !p->d_xm;
-    if (int rc = half_alloc(&p->d_xm, bytes)) return rc;
-    if (fresh) p->bytes_solve_many = bytes;
-    return SF_OK;
-}
-
-int half_qf_scratch(sf_chol_plan* p) { return half_alloc(&p->d_qf, (size_t)(sf::QF_MAXB + 1) * sf::SVM_W * sizeof(double)); }
-
-// one half of the solve on x (the sync block is cleared here): the forward steps, or the backward sweep
-int half_sweep(sf_chol_plan* p, int which, double* x, int width, bool transpose_diag, hipStream_t st) {
-    const SolveSync y = sf_solve_sync(p);
-    HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, y.bytes, st));
-    if (which == SF_HALF_L) {
-        for (size_t k = 0; k < p->solve_steps.size(); ++k) sf_solve_step_fwd(p, k, p->d_Lsx, x, width, y, st);
-    } else {
-        sf_solve_sweep_bwd(p, x, width, transpose_diag, y, st);
-    }
-    return SF_OK;
-}
-
-// a chunk of cw columns between the host (column-major, leading dimension ld) and the staging half
-int half_stage_in(const double* B, sf_long ld, int64_t n, int cw, double* stage, hipStream_t st) {
-    if (ld == n) {
-        HIP_TRY(hipMemcpyAsync(stage, B, (size_t)n * cw * sizeof(double), hipMemcpyHostToDevice, st));
-    } else {
-        for (int c = 0; c < cw; ++c)
-            HIP_TRY(hipMemcpyAsync(stage + (size_t)c * n, B + (size_t)c * ld, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    return SF_OK;
-}
-int half_stage_out(double* X, sf_long ld, int64_t n, int cw, const double* stage, hipStream_t st) {
-    if (ld == n) {
-        HIP_TRY(hipMemcpyAsync(X, stage, (size_t)n * cw * sizeof(double), hipMemcpyDeviceToHost, st));
-    } else {
-        for (int c = 0; c < cw; ++c)
-            HIP_TRY(hipMemcpyAsync(X + (size_t)c * ld, stage + (size_t)c * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    return SF_OK;
-}
-
-// the stretch between the plan's solve events, added to *total
-void half_add_ms(sf_chol_plan* p, double* total) {
-    float ms = 0;
-    if (elapsed_ms(&ms, p->ev_s0, p->ev_s1)) *total += ms;
-}
-
 }  // namespace
-
-int sf_quadform_scratch(sf_chol_plan* p) { return half_qf_scratch(p); }
 
 extern "C" {
 
@@ -241,40 +175,17 @@ int sf_chol_plan_solve_half(sf_chol_plan* p, int which, sf_long nrhs, const sf_f
     bool go = false;
     if (int rc = half_begin(p, nrhs, &go)) return rc;
     if (!go) return SF_OK;
-    hipStream_t st = p->stream;
-    const int64_t n = p->n;
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    double total_ms = 0;
-    if (nrhs == 1) {
-        // the one-column family on d_x
-        HIP_TRY(hipMemcpyAsync(p->d_x, B, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(e0, st));
-        if (int rc = half_sweep(p, which, p->d_x, 1, true, st)) return rc;
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(X, p->d_x, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        half_add_ms(p, &total_ms);
-        p->last_half_ms = total_ms;
-        return SF_OK;
-    }
-    if (int rc = half_block(p)) return rc;
-    const int W = sf::SVM_W;
-    double* stage = p->d_xm + (size_t)n * W;
-    for (sf_long j0 = 0; j0 < nrhs; j0 += W) {
-        const int cw = (int)std::min<sf_long>(W, nrhs - j0);
-        if (int rc = half_stage_in(B + j0 * ldb, ldb, n, cw, stage, st)) return rc;
-        HIP_TRY(hipEventRecord(e0, st));
-        sf::launch_solve_many_pack(stage, n, cw, p->d_xm, st);
-        if (int rc = half_sweep(p, which, p->d_xm, W, j0 == 0, st)) return rc;     // (the diagonal blocks' row-major copies: once per call)
-        sf::launch_solve_many_unpack(p->d_xm, n, cw, stage, st);
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        if (int rc = half_stage_out(X + j0 * ldx, ldx, n, cw, stage, st)) return rc;
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        half_add_ms(p, &total_ms);
-    }
-    p->last_half_ms = total_ms;
+    const int W = nrhs == 1 ? 1 : sf::SVM_W;        // (one column: the one-column family on d_x)
+    if (W > 1)
+        if (int rc = sf_solve_many_block(p)) return rc;
+    const SfSweep op = which == SF_HALF_L ? SF_SWEEP_FWD_L : SF_SWEEP_BWD;
+    const SfCols src{const_cast<double*>(B), ldb, false, nullptr}, dst{X, ldx, false, nullptr};
+    SfStretch t{p};
+    // (the diagonal blocks' row-major copies: once per call)
+    if (int rc = sf_apply_chunks(p, SfApply{&src, &dst, nrhs, W, W == 1 ? p->d_x : p->d_xm, 0, true}, t,
+                                 [&](double* x, sf_long j0, int) { return sf_apply_sweep(p, op, x, W, j0 == 0); }))
+        return rc;
+    p->last_half_ms = t.total_ms;
     return SF_OK;
 }
 
@@ -287,31 +198,27 @@ int sf_chol_plan_quadform(sf_chol_plan* p, sf_long nrhs, const sf_float* B, sf_l
         for (sf_long j = 0; j < nrhs; ++j) q[j] = 0.0;      // (n == 0: the empty sum)
         return SF_OK;
     }
-    if (int rc = half_qf_scratch(p)) return rc;
+    if (int rc = sf_quadform_scratch(p)) return rc;
     hipStream_t st = p->stream;
-    const int64_t n = p->n;
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    double total_ms = 0;
     const int W = nrhs == 1 ? 1 : sf::SVM_W;
     if (W > 1)
-        if (int rc = half_block(p)) return rc;
-    double* x = W == 1 ? p->d_x : p->d_xm;
-    double* stage = W == 1 ? p->d_x : p->d_xm + (size_t)n * W;      // (one column: loaded where the sweep works)
+        if (int rc = sf_solve_many_block(p)) return rc;
     const double* d_q = p->d_qf + (size_t)sf::QF_MAXB * W;
-    for (sf_long j0 = 0; j0 < nrhs; j0 += W) {
-        const int cw = (int)std::min<sf_long>(W, nrhs - j0);
-        if (int rc = half_stage_in(B + j0 * ldb, ldb, n, cw, stage, st)) return rc;
-        HIP_TRY(hipEventRecord(e0, st));
-        if (W > 1) sf::launch_solve_many_pack(stage, n, cw, x, st);
-        if (int rc = half_sweep(p, SF_HALF_L, x, W, false, st)) return rc;
-        sf::launch_quadform(x, n, W, p->d_qf, st);
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(q + j0, d_q, (size_t)cw * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        half_add_ms(p, &total_ms);
-    }
-    p->last_quadform_ms = total_ms;
+    const SfCols src{const_cast<double*>(B), ldb, false, nullptr};
+    SfStretch t{p};
+    if (int rc = sf_apply_chunks(
+            p, SfApply{&src, nullptr, nrhs, W, W == 1 ? p->d_x : p->d_xm, 0, true}, t,
+            [&](double* x, sf_long, int) {
+                if (int rc = sf_apply_sweep(p, SF_SWEEP_FWD_L, x, W, false)) return rc;
+                sf::launch_quadform(x, p->n, W, p->d_qf, st);
+                return SF_OK;
+            },
+            [&](double*, sf_long j0, int cw) {
+                HIP_TRY(hipMemcpyAsync(q + j0, d_q, (size_t)cw * sizeof(double), hipMemcpyDeviceToHost, st));
+                return SF_OK;
+            }))
+        return rc;
+    p->last_quadform_ms = t.total_ms;
     return SF_OK;
 }
 
@@ -323,37 +230,27 @@ int sf_chol_plan_sample(sf_chol_plan* p, sf_long nsamples, uint64_t seed, uint64
     bool go = false;
     if (int rc = half_begin(p, nsamples, &go)) return rc;
     if (!go) return SF_OK;
-    if (int rc = half_block(p)) return rc;
+    if (int rc = sf_solve_many_block(p)) return rc;
     hipStream_t st = p->stream;
-    const int64_t n = p->n;
     const int W = sf::SVM_W;
-    double* stage = p->d_xm + (size_t)n * W;
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    double total_ms = 0;
-    for (sf_long j0 = 0; j0 < nsamples; j0 += W) {
-        const int cw = (int)std::min<sf_long>(W, nsamples - j0);
-        HIP_TRY(hipEventRecord(e0, st));
-        sf::launch_sample_fill(p->d_xm, n, cw, seed, first_sample + (uint64_t)j0, st);
-        if (Z) {
-            // the normals leave through the staging half before the sweep overwrites the block; their copy is not device time, so
-            // the timed stretch ends here and a second one holds the sweep
-            sf::launch_solve_many_unpack(p->d_xm, n, cw, stage, st);
-            HIP_TRY(hipEventRecord(e1, st));
-            HIP_TRY(hipGetLastError());
-            if (int rc = half_stage_out(Z + j0 * ldz, ldz, n, cw, stage, st)) return rc;
-            HIP_TRY(hipStreamSynchronize(st));
-            half_add_ms(p, &total_ms);
-            HIP_TRY(hipEventRecord(e0, st));
-        }
-        if (int rc = half_sweep(p, SF_HALF_LT, p->d_xm, W, j0 == 0, st)) return rc;
-        sf::launch_solve_many_unpack(p->d_xm, n, cw, stage, st);
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        if (int rc = half_stage_out(X + j0 * ldx, ldx, n, cw, stage, st)) return rc;
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        half_add_ms(p, &total_ms);
-    }
-    p->last_sample_ms = total_ms;
+    double* stage = p->d_xm + (size_t)p->n * W;
+    const SfCols dst{X, ldx, false, nullptr}, zdst{Z, ldz, false, nullptr};
+    SfStretch t{p};
+    if (int rc = sf_apply_chunks(p, SfApply{nullptr, &dst, nsamples, W, p->d_xm, 0, true}, t, [&](double* x, sf_long j0, int cw) {
+            sf::launch_sample_fill(x, p->n, cw, seed, first_sample + (uint64_t)j0, st);
+            if (Z) {
+                // the normals leave through the staging half before the sweep overwrites the block; their copy is not device time,
+                // so the timed stretch ends here and a second one holds the sweep
+                sf_cols_store(p, zdst, j0, cw, W, x, stage);
+                if (int rc = t.mark()) return rc;
+                if (int rc = sf_cols_stage_out(p, zdst, j0, cw, stage)) return rc;
+                if (int rc = t.close(false)) return rc;
+                if (int rc = t.open()) return rc;
+            }
+            return sf_apply_sweep(p, SF_SWEEP_BWD, x, W, j0 == 0);
+        }))
+        return rc;
+    p->last_sample_ms = t.total_ms;
     return SF_OK;
 }
 

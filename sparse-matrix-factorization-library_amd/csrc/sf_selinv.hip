@@ -248,10 +248,6 @@ namespace {
 
 using sf::SelUnit;
 
-bool selinv_refused(const sf_chol_plan* p) {
-    return p->dry || p->lu || p->partial || p->nranks > 1 || p->ooc_groups > 1 || (p->nsuper > 0 && !p->d_solve);
-}
-
 int64_t slabs_for(int64_t tiles, int64_t K) {
     if (tiles <= 0 || tiles >= 256 || K < 512) return 1;         // (a unit with no rows below: no product at all)
     return std::max<int64_t>(1, std::min<int64_t>({sf::SEL_MAX_SLABS, (256 + tiles - 1) / tiles, K / 256}));
@@ -411,7 +407,7 @@ void run_big(sf_chol_plan* p, const sf_chol_plan::SelBig& b, hipStream_t st) {
 extern "C" {
 
 int sf_chol_plan_selinv(sf_chol_plan* p) {
-    if (!p || selinv_refused(p)) return SF_ERR_ARG;
+    if (!p || p->lu || !sf_plan_whole_resident(p)) return SF_ERR_ARG;
     if (!sf_selinv_factor_current(p)) return SF_ERR_ARG;
     if (p->n <= 0) return SF_OK;
     HIP_TRY(hipSetDevice(p->device));
@@ -441,7 +437,7 @@ int sf_chol_plan_selinv(sf_chol_plan* p) {
 }
 
 int sf_chol_plan_get_selinv_range(sf_chol_plan* p, sf_long e_begin, sf_long e_end, sf_float* out) {
-    if (!p || selinv_refused(p) || e_begin < 0 || e_end > p->xsize || e_end < e_begin || (!out && e_end > e_begin)) return SF_ERR_ARG;
+    if (!p || p->lu || !sf_plan_whole_resident(p) || e_begin < 0 || e_end > p->xsize || e_end < e_begin || (!out && e_end > e_begin)) return SF_ERR_ARG;
     if (!p->d_sel || p->sel_gen != p->factor_gen) return SF_ERR_ARG;
     if (e_end == e_begin) return SF_OK;
     HIP_TRY(hipSetDevice(p->device));
@@ -451,7 +447,7 @@ int sf_chol_plan_get_selinv_range(sf_chol_plan* p, sf_long e_begin, sf_long e_en
 }
 
 int sf_chol_plan_selinv_diag(sf_chol_plan* p, sf_float* d) {
-    if (!p || selinv_refused(p) || (!d && p->n > 0)) return SF_ERR_ARG;
+    if (!p || p->lu || !sf_plan_whole_resident(p) || (!d && p->n > 0)) return SF_ERR_ARG;
     if (p->n <= 0) return SF_OK;
     if (!p->d_sel || p->sel_gen != p->factor_gen) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
@@ -463,7 +459,7 @@ int sf_chol_plan_selinv_diag(sf_chol_plan* p, sf_float* d) {
 }
 
 int sf_chol_plan_logdet(sf_chol_plan* p, sf_float* out) {
-    if (!p || !out || selinv_refused(p)) return SF_ERR_ARG;
+    if (!p || !out || p->lu || !sf_plan_whole_resident(p)) return SF_ERR_ARG;
     if (!sf_selinv_factor_current(p)) return SF_ERR_ARG;
     *out = 0.0;
     if (p->n <= 0) return SF_OK;

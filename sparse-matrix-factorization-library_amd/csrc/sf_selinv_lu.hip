@@ -297,11 +297,6 @@ namespace {
 
 using sf::SelUnit;
 
-// plan kinds neither entry point takes (pivoting is the caller's business: selinv refuses it, logdet does not)
-bool lu_selinv_refused(const sf_chol_plan* p) {
-    return p->dry || !p->lu || p->partial || p->nranks > 1 || p->ooc_groups > 1 || (p->nsuper > 0 && !p->d_solve);
-}
-
 // the scratch of the wide units, in d_sel_scratch
 struct LuScratch { double *Tl, *Tu, *Yl, *Yu, *Zl, *Zu, *Zsl, *Ssl, *Sc; };
 
@@ -412,7 +407,7 @@ int permutation_sign(const std::vector<sf_long>& pivpos) {
 extern "C" {
 
 int sf_lu_plan_selinv(sf_lu_plan* p) {
-    if (!p || lu_selinv_refused(p) || p->piv_tol > 0.0) return SF_ERR_ARG;
+    if (!p || !p->lu || !sf_plan_whole_resident(p) || p->piv_tol > 0.0) return SF_ERR_ARG;
     if (!sf_selinv_factor_current(p)) return SF_ERR_ARG;
     if (p->n <= 0) return SF_OK;
     HIP_TRY(hipSetDevice(p->device));
@@ -442,7 +437,7 @@ int sf_lu_plan_selinv(sf_lu_plan* p) {
 }
 
 int sf_lu_plan_get_selinv_range(sf_lu_plan* p, sf_long e_begin, sf_long e_end, sf_float* out) {
-    if (!p || lu_selinv_refused(p) || e_begin < 0 || e_end > p->xsize || e_end < e_begin || (!out && e_end > e_begin)) return SF_ERR_ARG;
+    if (!p || !p->lu || !sf_plan_whole_resident(p) || e_begin < 0 || e_end > p->xsize || e_end < e_begin || (!out && e_end > e_begin)) return SF_ERR_ARG;
     if (!p->d_sel || p->sel_gen != p->factor_gen) return SF_ERR_ARG;
     if (e_end == e_begin) return SF_OK;
     HIP_TRY(hipSetDevice(p->device));
@@ -462,7 +457,7 @@ int sf_lu_plan_get_selinv_range(sf_lu_plan* p, sf_long e_begin, sf_long e_end, s
 }
 
 int sf_lu_plan_selinv_diag(sf_lu_plan* p, sf_float* d) {
-    if (!p || lu_selinv_refused(p) || (!d && p->n > 0)) return SF_ERR_ARG;
+    if (!p || !p->lu || !sf_plan_whole_resident(p) || (!d && p->n > 0)) return SF_ERR_ARG;
     if (p->n <= 0) return SF_OK;
     if (!p->d_sel || p->sel_gen != p->factor_gen) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
@@ -474,7 +469,7 @@ int sf_lu_plan_selinv_diag(sf_lu_plan* p, sf_float* d) {
 }
 
 int sf_lu_plan_logdet(sf_lu_plan* p, sf_float* logabs, int* sign) {
-    if (!p || !logabs || lu_selinv_refused(p)) return SF_ERR_ARG;
+    if (!p || !logabs || !p->lu || !sf_plan_whole_resident(p)) return SF_ERR_ARG;
     if (!sf_selinv_factor_current(p)) return SF_ERR_ARG;
     *logabs = 0.0;
     if (sign) *sign = 1;

@@ -769,75 +769,39 @@ int sf_chol_plan_solve(sf_chol_plan* p, const sf_float* b_host, sf_float* x_host
     if (p->partial || (p->nsuper > 0 && !p->d_solve)) return SF_ERR_ARG;
     if (p->dry) return SF_ERR_ARG;        // a schedule-only plan has no device side
     HIP_TRY(hipSetDevice(p->device));
-    hipStream_t st = p->stream;
     if (p->n <= 0) return SF_OK;
-    HIP_TRY(hipMemcpyAsync(p->d_x, b_host, p->n * sizeof(double), hipMemcpyHostToDevice, st));
-    // the plan's own event pair (ev0/ev1 time the factorization; sf_chol_plan_sync has read them by now): nothing is
-    // created here, so an error return leaks nothing
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    HIP_TRY(hipEventRecord(e0, st));
-    HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, sf_solve_sync(p).bytes, st));
-    sf_solve_sweeps(p, p->d_x, 1, true, st);
-    HIP_TRY(hipEventRecord(e1, st));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(x_host, p->d_x, p->n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (int rc = sf_solve_finish(p, st)) return rc;
-    float ms = 0;
-    if (elapsed_ms(&ms, e0, e1)) p->last_solve_ms = ms;
+    const SfCols src{const_cast<double*>(b_host), p->n, false, nullptr}, dst{x_host, p->n, false, nullptr};
+    SfStretch t{p};
+    if (int rc = sf_apply_chunks(p, SfApply{&src, &dst, 1, 1, p->d_x, 0, true}, t,
+                                 [&](double* x, sf_long, int) { return sf_apply_sweep(p, SF_SWEEP_SOLVE, x, 1, true); }))
+        return rc;
+    if (t.timed) p->last_solve_ms = t.total_ms;
     return SF_OK;
 }
 
 // X <- (L L^T)^{-1} B (LU: (L U)^{-1} B) for nrhs columns, SVM_W of them per forward + backward sweep.  A chunk goes H2D
-// column-major into the staging half of d_xm (one copy when ldb == n, one per column otherwise), a small kernel transposes it
+// column-major into the staging half of d_xm (one copy when ldb == n, one 2-D copy otherwise), a small kernel transposes it
 // into the row-major block the sweep kernels work on (zero columns pad a partial chunk), and the way back is the same in
-// reverse.  Row-major on the device because every row a tile gathers or scatters through Lsi is then one 128-byte run; the
-// transposes run on the device, where they cost two streaming passes over n x SVM_W doubles, instead of as strided host loops
-// or 2-D copies with 8-byte pieces.
+// reverse (sf_apply_chunks).  Row-major on the device because every row a tile gathers or scatters through Lsi is then one
+// 128-byte run; the transposes run on the device, where they cost two streaming passes over n x SVM_W doubles, instead of as
+// strided host loops or 2-D copies with 8-byte pieces.
 int sf_chol_plan_solve_many(sf_chol_plan* p, sf_long nrhs, const sf_float* B, sf_long ldb, sf_float* X, sf_long ldx) {
     if (!p || !B || !X || nrhs < 0) return SF_ERR_ARG;
+    // (not sf_plan_whole_resident: this entry point has never looked at nranks)
     if (p->dry || p->partial || p->ooc_groups > 1 || (p->nsuper > 0 && !p->d_solve)) return SF_ERR_ARG;
     const sf_long ldmin = std::max<sf_long>(p->n, 1);
     if (ldb < ldmin || ldx < ldmin) return SF_ERR_ARG;
     if ((const void*)X == (const void*)B && ldx != ldb) return SF_ERR_ARG;
     if (nrhs == 0 || p->n <= 0) return SF_OK;
     HIP_TRY(hipSetDevice(p->device));
-    hipStream_t st = p->stream;
-    const int64_t n = p->n;
-    const int W = sf::SVM_W;
-    if (!p->d_xm) {
-        const size_t bytes = 2 * (size_t)n * W * sizeof(double);
-        HIP_TRY(hipMalloc((void**)&p->d_xm, bytes));
-        p->bytes_solve_many = bytes;
-    }
-    double* stage = p->d_xm + (size_t)n * W;
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    double total_ms = 0;
-    for (sf_long j0 = 0; j0 < nrhs; j0 += W) {
-        const int cw = (int)std::min<sf_long>(W, nrhs - j0);
-        if (ldb == n) {
-            HIP_TRY(hipMemcpyAsync(stage, B + j0 * ldb, (size_t)n * cw * sizeof(double), hipMemcpyHostToDevice, st));
-        } else {
-            for (int c = 0; c < cw; ++c)
-                HIP_TRY(hipMemcpyAsync(stage + (size_t)c * n, B + (j0 + c) * ldb, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-        }
-        HIP_TRY(hipEventRecord(e0, st));
-        sf::launch_solve_many_pack(stage, n, cw, p->d_xm, st);
-        HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, sf_solve_sync(p).bytes, st));
-        sf_solve_sweeps(p, p->d_xm, W, j0 == 0, st);       // (the row-major copies of the diagonal blocks: once per call)
-        sf::launch_solve_many_unpack(p->d_xm, n, cw, stage, st);
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        if (ldx == n) {
-            HIP_TRY(hipMemcpyAsync(X + j0 * ldx, stage, (size_t)n * cw * sizeof(double), hipMemcpyDeviceToHost, st));
-        } else {
-            for (int c = 0; c < cw; ++c)
-                HIP_TRY(hipMemcpyAsync(X + (j0 + c) * ldx, stage + (size_t)c * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        float ms = 0;
-        if (elapsed_ms(&ms, e0, e1)) total_ms += ms;
-    }
-    p->last_solve_many_ms = total_ms;
+    if (int rc = sf_solve_many_block(p)) return rc;
+    const SfCols src{const_cast<double*>(B), ldb, false, nullptr}, dst{X, ldx, false, nullptr};
+    SfStretch t{p};
+    // (the row-major copies of the diagonal blocks: once per call)
+    if (int rc = sf_apply_chunks(p, SfApply{&src, &dst, nrhs, sf::SVM_W, p->d_xm, 0, true}, t,
+                                 [&](double* x, sf_long j0, int) { return sf_apply_sweep(p, SF_SWEEP_SOLVE, x, sf::SVM_W, j0 == 0); }))
+        return rc;
+    p->last_solve_many_ms = t.total_ms;
     return SF_OK;
 }
 

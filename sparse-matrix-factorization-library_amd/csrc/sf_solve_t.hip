@@ -438,20 +438,10 @@ void launch_condest_argmax_next(double* x, int64_t n, CondScalars* s, int first,
 // ---------------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------------
-namespace {
-
-// the plans the transposed solves and the condition estimate run on: whole and resident
-bool tsolve_refused(const sf_chol_plan* p) {
-    return p->dry || p->partial || p->nranks > 1 || p->ooc_groups > 1 || (p->nsuper > 0 && !p->d_solve);
-}
-
-}  // namespace
-
 // x <- A^{-T} x for an LU plan (the caller has zeroed the sync block on the stream), in its two halves.  The row-major copies of the
 // top steps' diagonal blocks (d_solveT) are made from the PL base by the second half, on every call that asks for them; their
 // diagonal entries are copied too and simply not read.  sf_solve_sweep_bwd remakes them from PU at the start of every solve /
-// solve_many / refine call, so neither sweep ever sees the other's copies -- keep it that way: a caller that alternates the two
-// (the condition estimate, the half solves of sf_gram_lu.hip) must ask BOTH for their copies every time.
+// solve_many / refine call, so neither sweep ever sees the other's copies (sf_apply_sweep states the rule for its callers).
 // (U^T)^{-1}: the plain forward kernels on the other panel set -- non-unit diagonal, no interchanges
 void tsolve_sweep_fwd(sf_chol_plan* p, double* x, int width, const SolveSync& y, hipStream_t st) {
     const double* PU = p->d_Lsx + p->xC;
@@ -493,7 +483,7 @@ void tsolve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, h
 namespace {
 
 int condest(sf_chol_plan* p, sf_float* anorm, sf_float* ainv_norm_est) {
-    if (tsolve_refused(p) || !p->values_set) return SF_ERR_ARG;
+    if (!sf_plan_whole_resident(p) || !p->values_set) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     if (!sf_factor_usable(p)) return SF_ERR_ARG;
     *anorm = 0.0;
@@ -512,17 +502,14 @@ int condest(sf_chol_plan* p, sf_float* anorm, sf_float* ainv_norm_est) {
     double* x = p->d_cond;
     double* xi = x + n;
     sf::CondScalars* ds = (sf::CondScalars*)(xi + n);
-    const size_t sync_bytes = sf_solve_sync(p).bytes;
     int solves = 0;
     bool solve_failed = false;
     // A^{-1} x and A^{-T} x in place.  LU: each sweep pair makes its own row-major diagonal copies (see tsolve_sweeps); Cholesky: the
     // plain sweeps serve for both (A = A^T) and the first one's copies stay good.
     auto sweep = [&](bool transposed) -> int {
-        HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, sync_bytes, st));
-        if (transposed && p->lu) tsolve_sweeps(p, x, 1, true, st);
-        else sf_solve_sweeps(p, x, 1, p->lu || solves == 0, st);
+        const bool trans = transposed && p->lu;
         ++solves;
-        return SF_OK;
+        return sf_apply_sweep(p, trans ? SF_SWEEP_TRANS : SF_SWEEP_SOLVE, x, 1, p->lu || solves == 1);
     };
     // the one 16-byte copy and the one synchronisation of an iteration
     sf::CondScalars h;
@@ -586,72 +573,37 @@ extern "C" {
 
 int sf_lu_plan_solve_transposed(sf_lu_plan* p, const sf_float* b_host, sf_float* x_host) {
     if (!p || !b_host || !x_host) return SF_ERR_ARG;
-    if (!p->lu || tsolve_refused(p)) return SF_ERR_ARG;
+    if (!p->lu || !sf_plan_whole_resident(p)) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     if (!sf_factor_usable(p)) return SF_ERR_ARG;
-    hipStream_t st = p->stream;
     if (p->n <= 0) return SF_OK;
-    HIP_TRY(hipMemcpyAsync(p->d_x, b_host, p->n * sizeof(double), hipMemcpyHostToDevice, st));
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    HIP_TRY(hipEventRecord(e0, st));
-    HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, sf_solve_sync(p).bytes, st));
-    tsolve_sweeps(p, p->d_x, 1, true, st);
-    HIP_TRY(hipEventRecord(e1, st));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(x_host, p->d_x, p->n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (int rc = sf_solve_finish(p, st)) return rc;
-    float ms = 0;
-    if (elapsed_ms(&ms, e0, e1)) p->last_solve_ms = ms;
+    const SfCols src{const_cast<double*>(b_host), p->n, false, nullptr}, dst{x_host, p->n, false, nullptr};
+    SfStretch t{p};
+    if (int rc = sf_apply_chunks(p, SfApply{&src, &dst, 1, 1, p->d_x, 0, true}, t,
+                                 [&](double* x, sf_long, int) { return sf_apply_sweep(p, SF_SWEEP_TRANS, x, 1, true); }))
+        return rc;
+    if (t.timed) p->last_solve_ms = t.total_ms;
     return SF_OK;
 }
 
 // sf_chol_plan_solve_many's chunking, staging and layouts (see there), the transposed sweeps in the middle
 int sf_lu_plan_solve_many_transposed(sf_lu_plan* p, sf_long nrhs, const sf_float* B, sf_long ldb, sf_float* X, sf_long ldx) {
     if (!p || !B || !X || nrhs < 0) return SF_ERR_ARG;
-    if (!p->lu || tsolve_refused(p)) return SF_ERR_ARG;
+    if (!p->lu || !sf_plan_whole_resident(p)) return SF_ERR_ARG;
     const sf_long ldmin = std::max<sf_long>(p->n, 1);
     if (ldb < ldmin || ldx < ldmin) return SF_ERR_ARG;
     if ((const void*)X == (const void*)B && ldx != ldb) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     if (!sf_factor_usable(p)) return SF_ERR_ARG;
     if (nrhs == 0 || p->n <= 0) return SF_OK;
-    hipStream_t st = p->stream;
-    const int64_t n = p->n;
-    const int W = sf::SVM_W;
-    if (!p->d_xm) {
-        const size_t bytes = 2 * (size_t)n * W * sizeof(double);
-        HIP_TRY(hipMalloc((void**)&p->d_xm, bytes));
-        p->bytes_solve_many = bytes;
-    }
-    double* stage = p->d_xm + (size_t)n * W;
-    hipEvent_t e0 = p->ev_s0, e1 = p->ev_s1;
-    double total_ms = 0;
-    for (sf_long j0 = 0; j0 < nrhs; j0 += W) {
-        const int cw = (int)std::min<sf_long>(W, nrhs - j0);
-        if (ldb == n) {
-            HIP_TRY(hipMemcpyAsync(stage, B + j0 * ldb, (size_t)n * cw * sizeof(double), hipMemcpyHostToDevice, st));
-        } else {
-            for (int c = 0; c < cw; ++c)
-                HIP_TRY(hipMemcpyAsync(stage + (size_t)c * n, B + (j0 + c) * ldb, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-        }
-        HIP_TRY(hipEventRecord(e0, st));
-        sf::launch_solve_many_pack(stage, n, cw, p->d_xm, st);
-        HIP_TRY(hipMemsetAsync(p->d_solve_sync, 0, sf_solve_sync(p).bytes, st));
-        tsolve_sweeps(p, p->d_xm, W, j0 == 0, st);          // (the row-major copies of the diagonal blocks: once per call)
-        sf::launch_solve_many_unpack(p->d_xm, n, cw, stage, st);
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipGetLastError());
-        if (ldx == n) {
-            HIP_TRY(hipMemcpyAsync(X + j0 * ldx, stage, (size_t)n * cw * sizeof(double), hipMemcpyDeviceToHost, st));
-        } else {
-            for (int c = 0; c < cw; ++c)
-                HIP_TRY(hipMemcpyAsync(X + (j0 + c) * ldx, stage + (size_t)c * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        if (int rc = sf_solve_finish(p, st)) return rc;
-        float ms = 0;
-        if (elapsed_ms(&ms, e0, e1)) total_ms += ms;
-    }
-    p->last_solve_many_ms = total_ms;
+    if (int rc = sf_solve_many_block(p)) return rc;
+    const SfCols src{const_cast<double*>(B), ldb, false, nullptr}, dst{X, ldx, false, nullptr};
+    SfStretch t{p};
+    // (the row-major copies of the diagonal blocks: once per call)
+    if (int rc = sf_apply_chunks(p, SfApply{&src, &dst, nrhs, sf::SVM_W, p->d_xm, 0, true}, t,
+                                 [&](double* x, sf_long j0, int) { return sf_apply_sweep(p, SF_SWEEP_TRANS, x, sf::SVM_W, j0 == 0); }))
+        return rc;
+    p->last_solve_many_ms = t.total_ms;
     return SF_OK;
 }
 

@@ -162,6 +162,9 @@ def test_layouts():
         Bi = np.asfortranarray(B.copy())
         assert lib.sf_chol_plan_solve_half(plan._h, w, k, _dp(Bi), n, _dp(Bi), n) == SF_OK
         assert same(Bi)
+        Bq = Bp.copy(order="F")
+        assert lib.sf_chol_plan_solve_half(plan._h, w, k, _dp(Bq), ldb, _dp(Bq), ldb) == SF_OK        # in place, padded
+        assert same(Bq[:n]) and np.all(Bq[n:] == 7.0)
         assert lib.sf_chol_plan_solve_half(plan._h, w, k, _dp(Bp), ldb, _dp(Bp), ldb + 1) == SF_ERR_ARG
         # nrhs == 0 and a wrong first dimension
         assert lib.sf_chol_plan_solve_half(plan._h, w, 0, _dp(Bp), ldb, _dp(Xp), ldx) == SF_OK
@@ -182,6 +185,9 @@ def test_layouts():
     assert lib.sf_chol_plan_quadform(plan._h, k, _dp(Bp), ldb, _dp(q)) == SF_OK
     assert np.allclose(q[:k], qref, rtol=1e-13, atol=0.0) and np.all(q[k:] == -3.0)
     assert lib.sf_chol_plan_quadform(plan._h, 0, _dp(Bp), ldb, _dp(q)) == SF_OK and np.all(q[k:] == -3.0)
+    q1 = np.full(2, -3.0)
+    assert lib.sf_chol_plan_quadform(plan._h, 1, _dp(Bp), ldb, _dp(q1)) == SF_OK        # one column of the padded block
+    assert np.allclose(q1[0], qref[0], rtol=1e-13, atol=0.0) and q1[1] == -3.0
     assert plan.quadform(np.empty((n, 0))).shape == (0,)
     with pytest.raises(ValueError):
         plan.quadform(np.ones((n + 1, 2)))

@@ -198,6 +198,12 @@ def test_layouts_in_place_and_stats():
         Xp = np.full((ldx, k), -3.0, order="F")
         assert lib.sf_lu_plan_solve_half(plan._h, code, k, _dp(Bp), ldb, _dp(Xp), ldx) == SF_OK
         assert same(Xp[:n]) and np.all(Xp[n:] == -3.0) and np.all(Bp[n:] == 7.0)
+        x1 = np.full(ldx, -3.0)
+        assert lib.sf_lu_plan_solve_half(plan._h, code, 1, _dp(Bp), ldb, _dp(x1), ldx) == SF_OK        # one column of the padded block
+        assert same(np.column_stack([x1[:n], ref[:, 1:]])) and np.all(x1[n:] == -3.0)
+        Bq = Bp.copy(order="F")
+        assert lib.sf_lu_plan_solve_half(plan._h, code, k, _dp(Bq), ldb, _dp(Bq), ldb) == SF_OK        # in place, padded
+        assert same(Bq[:n]) and np.all(Bq[n:] == 7.0)
         Bi = np.asfortranarray(B.copy())
         assert lib.sf_lu_plan_solve_half(plan._h, code, k, _dp(Bi), n, _dp(Bi), n) == SF_OK        # in place
         assert same(Bi)

@@ -255,6 +255,9 @@ def test_layouts_and_stats():
     Xp = np.full((ldx, k), -3.0, order="F")
     assert sf.lib.sf_lu_plan_solve_many_transposed(plan._h, k, dp(Bp), ldb, dp(Xp), ldx) == 0
     assert same(Xp[:n]) and np.all(Xp[n:] == -3.0)
+    x1 = np.full(ldx, -3.0)
+    assert sf.lib.sf_lu_plan_solve_many_transposed(plan._h, 1, dp(Bp), ldb, dp(x1), ldx) == 0       # one column of the padded block
+    assert same(np.column_stack([x1[:n], ref[:, 1:]])) and np.all(x1[n:] == -3.0)
     Bi = np.asfortranarray(B.copy())
     assert sf.lib.sf_lu_plan_solve_many_transposed(plan._h, k, dp(Bi), n, dp(Bi), n) == 0      # in place
     assert same(Bi)

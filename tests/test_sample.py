@@ -87,6 +87,10 @@ def test_flat_abi_leading_dimensions(lap16):
     assert sf.lib.sf_chol_plan_sample(plan._h, k, 5, 0, _dp(Xq), ldx, None, 0) == SF_OK
     assert np.abs(Xq[:n] - X[:, :k]).max() <= 1e-13 * np.abs(X).max() and np.all(Xq[n:] == -3.0)
     assert sf.lib.sf_chol_plan_sample(plan._h, 0, 5, 0, _dp(Xq), ldx, None, 0) == SF_OK
+    x1, z1 = np.full(ldx, -3.0), np.full(ldz, 7.0)
+    assert sf.lib.sf_chol_plan_sample(plan._h, 1, 5, 0, _dp(x1), ldx, _dp(z1), ldz) == SF_OK        # one sample
+    assert np.array_equal(z1[:n], Z[:, 0]) and np.all(z1[n:] == 7.0)
+    assert np.abs(x1[:n] - X[:, 0]).max() <= 1e-13 * np.abs(X).max() and np.all(x1[n:] == -3.0)
 
 
 def test_distribution_against_selinv():

@@ -166,6 +166,9 @@ def test_layouts():
     assert sf.lib.sf_chol_plan_solve_many(plan._h, k, _dp(Bp), ldb, _dp(Xp), ldx) == 0
     assert same(Xp[:n])
     assert np.all(Xp[n:] == -3.0)
+    x1 = np.full(ldx, -3.0)
+    assert sf.lib.sf_chol_plan_solve_many(plan._h, 1, _dp(Bp), ldb, _dp(x1), ldx) == 0       # one column of the padded block
+    assert same(np.column_stack([x1[:n], ref[:, 1:]])) and np.all(x1[n:] == -3.0)
     # in place, X = B
     Bi = np.asfortranarray(B.copy())
     assert sf.lib.sf_chol_plan_solve_many(plan._h, k, _dp(Bi), n, _dp(Bi), n) == 0

@@ -1,6 +1,8 @@
 """GPU only: the Schur complement of a border, G = B^T A^-1 B (`CholPlan.gram`), next to the library's existing kernels
 on ONE plan, 128^3 Cholesky, at k = 16, 64 and 256 columns.  Prints one JSON line; per k:
   gram             device ms of `gram` ("last_gram_ms": forward sweeps and reductions, copies excluded) and its wall time
+  gram_padded      --pad P: the same call through the C entry point with B in an array of leading dimension n + P (the chunks' way
+                   to the device is then a strided copy)
   solve_half_L     device ms of `solve_half(B, "L")` for the same k ("last_half_ms"): the same sweeps with an unpack kernel in place
                    of the reduction, so gram - solve_half_L is what the reduction costs beyond the unpack
   solve_many       device ms of `solve_many(B)` ("last_solve_many_ms"): both sweeps
@@ -96,6 +98,7 @@ def main():
     ap.add_argument("--ks", type=int, nargs="+", default=[16, 64, 256])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--reps-old", type=int, default=2)
+    ap.add_argument("--pad", type=int, default=0, help="also time the host call with ldb = n + PAD")
     a = ap.parse_args()
     if sf.device_count() < 1:
         raise SystemExit("gram_timing: no HIP device")
@@ -115,6 +118,17 @@ def main():
         r = {}
         g_dev, g_wall = timed(lambda: plan.gram(B), lambda: plan.stat("last_gram_ms"), a.reps)
         r["gram"], r["gram_wall"] = g_dev, g_wall
+        if a.pad:
+            Bp = np.zeros((n + a.pad, k), order="F")
+            Bp[:n] = B
+            Gp = np.zeros((k, k), order="F")
+            dp = lambda x: x.ctypes.data_as(C.POINTER(C.c_double))
+
+            def padded():
+                sf._lib.check(sf.lib.sf_chol_plan_gram(plan._h, k, dp(Bp), n + a.pad, dp(Gp), k), "sf_chol_plan_gram")
+
+            r["gram_padded"], r["gram_padded_wall"] = timed(padded, lambda: plan.stat("last_gram_ms"), a.reps)
+            del Bp
         r["parts"] = int(plan.stat("last_gram_parts"))
         r["bytes_gram"] = int(plan.stat("bytes_gram"))
         r["solve_half_L"], _ = timed(lambda: plan.solve_half(B, "L"), lambda: plan.stat("last_half_ms"), a.reps)
