@@ -148,7 +148,9 @@ int sf_chol_plan_selinv_diag(sf_chol_plan *plan, sf_float *d);
 /* log det A = 2 sum_j log L_jj of the resident factor, reduced on the device in a fixed order (independent of selinv) */
 int sf_chol_plan_logdet(sf_chol_plan *plan, sf_float *out);
 /* SparseFrame_validate on the device (C:3141-3266; LU plans: L:3702-3858): b_i = 1 + i/n, solve with the resident factor,
- * r = A x - b from the plan's copy of the matrix values, *residual = |r|_inf / (|A|_1 |x|_inf + |b|_inf).  x_host may be NULL. */
+ * r = A x - b from the plan's copy of the matrix values, *residual = |r|_inf / (|A|_1 |x|_inf + |b|_inf).  x_host may be NULL.
+ * *residual is NaN when any r_i or x_i is not finite (NaN fails every `<=`); the return code is SF_OK all the same.  The struct
+ * path's SparseFrame_validate (both libraries) sets matrix_info->residual by the same rule. */
 int sf_chol_plan_validate(sf_chol_plan *plan, sf_float *residual, sf_float *x_host);
 /* r = b - A x on the device with the plan's CURRENT matrix values (the last set_values; permuted space), for the caller's own b
  * and x.  With w = |A| |x| + |b|:

@@ -121,7 +121,8 @@ int SparseFrame_factorize_supernodal(struct common_info_struct *common_info, str
 
 /* replaces C:3036-3139 (host triangular solves, reads Lsx/Bx, writes Xx) */
 int SparseFrame_solve_supernodal(struct matrix_info_struct *matrix_info);
-/* replaces C:3141-3266 (b_i = 1 + i/n, residual |Ax-b|_inf / (|A|_1 |x|_inf + |b|_inf)) */
+/* replaces C:3141-3266 (b_i = 1 + i/n, residual |Ax-b|_inf / (|A|_1 |x|_inf + |b|_inf)); the residual is NaN when any r_i or
+ * x_i is not finite, the return code stays 0 */
 int SparseFrame_validate(struct matrix_info_struct *matrix_info);
 /* replaces C:3268-3321 */
 int SparseFrame_cleanup_matrix(struct matrix_info_struct *matrix_info);

@@ -134,7 +134,8 @@ sf_long SparseFrame_perturbed_pivots(const struct matrix_info_struct *matrix_inf
 
 /* replaces L:3592-3700 (host triangular solves, reads Lsx/Bx, writes Xx) */
 int SparseFrame_solve_supernodal(struct matrix_info_struct *matrix_info);
-/* replaces L:3702-3858 (b_i = 1 + i/n, residual |Ax-b|_inf / (|A|_1 |x|_inf + |b|_inf)) */
+/* replaces L:3702-3858 (b_i = 1 + i/n, residual |Ax-b|_inf / (|A|_1 |x|_inf + |b|_inf)); the residual is NaN when any r_i or
+ * x_i is not finite, the return code stays 0 */
 int SparseFrame_validate(struct matrix_info_struct *matrix_info);
 /* replaces L:3860-3922 */
 int SparseFrame_cleanup_matrix(struct matrix_info_struct *matrix_info);

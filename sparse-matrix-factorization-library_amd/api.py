@@ -438,7 +438,9 @@ class Schedule(_ScheduleMixin, _ShardedPlanMixin):
 
 class _ValidateMixin:
     def validate(self, return_x=False):
-        """SparseFrame_validate on the device: b_i = 1 + i/n, solve, residual |Ax - b|_inf / (|A|_1 |x|_inf + |b|_inf)"""
+        """SparseFrame_validate on the device: b_i = 1 + i/n, solve, residual |Ax - b|_inf / (|A|_1 |x|_inf + |b|_inf).
+        The residual is NaN when any r_i or x_i is not finite (a NaN fails every `<=`): a NaN that a kernel let through is
+        never reported as a perfect solve.  No exception is raised for it."""
         res = C.c_double()
         x = np.empty(max(self.n, 1), dtype=np.float64) if return_x else None
         check(lib.sf_chol_plan_validate(self._h, C.byref(res), _dp(x) if return_x else None), "sf_chol_plan_validate")
@@ -1294,6 +1296,8 @@ class MatrixInfo:
         check(self._lib.SparseFrame_factorize(C.byref(common.c), common.gpu_list, C.byref(self.c)), "SparseFrame_factorize")
 
     def validate(self):
+        """the struct path's residual |Ax - b|_inf / (|A|_1 |x|_inf + |b|_inf), b_i = 1 + i/n; NaN when any r_i or x_i is not
+        finite (the return code stays 0)"""
         check(self._lib.SparseFrame_validate(C.byref(self.c)), "SparseFrame_validate")
         return float(self.c.residual)
 

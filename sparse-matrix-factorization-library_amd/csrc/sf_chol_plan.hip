@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -678,7 +679,9 @@ int sf_chol_plan_validate(sf_chol_plan* p, sf_float* residual, sf_float* x_host)
     double h[4];
     HIP_TRY(hipMemcpyAsync(h, norms, sizeof(h), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
-    *residual = h[0] / (h[1] * h[2] + h[3]);
+    // k_resid_norms keeps a NaN (and an infinity) in its maxima: a non-finite r_i or x_i makes the residual NaN, which fails every
+    // `residual <= tol`; the return code stays SF_OK
+    *residual = (std::isfinite(h[0]) && std::isfinite(h[2])) ? h[0] / (h[1] * h[2] + h[3]) : std::numeric_limits<double>::quiet_NaN();
     if (x_host) memcpy(x_host, x.data(), p->n * sizeof(double));
     return SF_OK;
 }

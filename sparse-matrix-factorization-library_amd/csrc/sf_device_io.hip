@@ -94,7 +94,7 @@ k_dev_gather_values(const double* __restrict__ Ax, const int64_t* __restrict__ m
 
 // part[blk] = max |v[k]| over the entries this workgroup strides over (LU plans: the scale of the pivot perturbation, which
 // sf_lu_plan_set_values takes from its host array).  fmax drops a NaN, as std::max does there.
-constexpr int DIO_MAXB = 1024;
+// (DIO_MAXB, sf_kernels.h: workgroups at most, and so the size of the parts buffer)
 __global__ void __launch_bounds__(256)
 k_dev_absmax(const double* __restrict__ v, int64_t count, double* __restrict__ part) {
     __shared__ double red[256];
@@ -128,6 +128,17 @@ void launch_dev_unpack(const double* X, const int32_t* perm, int64_t n, int cw, 
     const dim3 g((unsigned)((n + DIO_ROWS - 1) / DIO_ROWS));
     if (perm) hipLaunchKernelGGL(k_dev_unpack<true>, g, dim3(256), 0, st, X, perm, n, cw, D, ldx);
     else hipLaunchKernelGGL(k_dev_unpack<false>, g, dim3(256), 0, st, X, perm, n, cw, D, ldx);
+}
+
+void launch_dev_gather_values(const double* Ax, const int64_t* map, int64_t count, double* out, hipStream_t st) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_dev_gather_values, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, Ax, map, count, out);
+}
+int launch_dev_absmax(const double* v, int64_t count, double* part, hipStream_t st) {
+    if (count <= 0) return 0;
+    const int nb = (int)std::min<int64_t>(DIO_MAXB, (count + 255) / 256);
+    hipLaunchKernelGGL(k_dev_absmax, dim3(nb), dim3(256), 0, st, v, count, part);
+    return nb;
 }
 
 }  // namespace sf
@@ -198,8 +209,7 @@ int dio_values_done(sf_chol_plan* p) {
         const int64_t cnt[2] = {p->nnz, p->u_alias ? 0 : p->unz};
         for (int k = 0; k < 2; ++k) {
             if (!src[k] || cnt[k] <= 0) continue;
-            nb[k] = (int)std::min<int64_t>(sf::DIO_MAXB, (cnt[k] + 255) / 256);
-            hipLaunchKernelGGL(sf::k_dev_absmax, dim3(nb[k]), dim3(256), 0, st, src[k], cnt[k], p->d_dio_part + (size_t)k * sf::DIO_MAXB);
+            nb[k] = sf::launch_dev_absmax(src[k], cnt[k], p->d_dio_part + (size_t)k * sf::DIO_MAXB, st);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(h.data() + (size_t)k * sf::DIO_MAXB, p->d_dio_part + (size_t)k * sf::DIO_MAXB, (size_t)nb[k] * sizeof(double),
                                    hipMemcpyDeviceToHost, st));
@@ -350,12 +360,8 @@ int sf_chol_plan_set_values_mapped_device(sf_chol_plan* p, const sf_float* dAx) 
     hipStream_t st = p->stream;
     const bool need_u = p->lu && !p->u_alias && p->unz > 0;
     const size_t nl = (size_t)std::max<int64_t>(p->nnz, 1);
-    if (p->nnz > 0)
-        hipLaunchKernelGGL(sf::k_dev_gather_values, dim3((unsigned)((p->nnz + 255) / 256)), dim3(256), 0, st, dAx, (const int64_t*)p->d_vmap,
-                           p->nnz, p->d_Lx);
-    if (need_u)
-        hipLaunchKernelGGL(sf::k_dev_gather_values, dim3((unsigned)((p->unz + 255) / 256)), dim3(256), 0, st, dAx,
-                           (const int64_t*)(p->d_vmap + nl), p->unz, p->d_Ux);
+    sf::launch_dev_gather_values(dAx, (const int64_t*)p->d_vmap, p->nnz, p->d_Lx, st);
+    if (need_u) sf::launch_dev_gather_values(dAx, (const int64_t*)(p->d_vmap + nl), p->unz, p->d_Ux, st);
     HIP_TRY(hipGetLastError());
     return dio_values_done(p);
 }

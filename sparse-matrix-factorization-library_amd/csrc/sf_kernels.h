@@ -235,6 +235,12 @@ void launch_dev_store1(const double* x, const int32_t* perm, int64_t n, double* 
 void launch_dev_pack(const double* B, int64_t ldb, const int32_t* perm, int64_t n, int cw, double* X, hipStream_t st);
 // and back: the columns [0, cw) of the block into the caller's chunk D
 void launch_dev_unpack(const double* X, const int32_t* perm, int64_t n, int cw, double* D, int64_t ldx, hipStream_t st);
+// values in the plan's order: out[p] = map[p] >= 0 ? Ax[map[p]] : 0.0 for p < count
+void launch_dev_gather_values(const double* Ax, const int64_t* map, int64_t count, double* out, hipStream_t st);
+// part[blk] = max |v[k]| over the entries workgroup blk strides over (a NaN is dropped); returns the number of parts written,
+// DIO_MAXB at most (0: count <= 0, nothing launched)
+constexpr int DIO_MAXB = 1024;
+int launch_dev_absmax(const double* v, int64_t count, double* part, hipStream_t st);
 
 // ---- the Gram matrix Y^T Y of the chunks of a half-solved border (sf_gram.hip, sf_chol_plan_gram) ----
 constexpr int GRAM_SLAB_ROWS = 2048;    // rows of a slab, about

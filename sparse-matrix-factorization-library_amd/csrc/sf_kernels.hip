@@ -1039,18 +1039,25 @@ k_resid_urows(const int64_t* __restrict__ Up, const int32_t* __restrict__ Ui, co
     if (ri != 0.0) unsafeAtomicAdd(r + i, ri);
 }
 
+// The maximum that KEEPS a NaN (fmax returns the other operand): a non-finite r_i or x_i -- a NaN that a factorization or solve
+// kernel let through -- must not be reported as a perfect solve.  The bit pattern of fabs(NaN) orders above +Inf, so the integer
+// atomicMax carries it into norms[] and the residual formed from them is NaN (Inf / Inf for an infinite x).  For non-negative
+// finite operands the result is fmax's, bit for bit.
+__device__ __forceinline__ double resid_max(double m, double v) { return (v > m || v != v) ? v : m; }
+
 __global__ void __launch_bounds__(256)
 k_resid_norms(int32_t n, const double* __restrict__ r, const double* __restrict__ colsum, const double* __restrict__ x,
               const double* __restrict__ b, unsigned long long* __restrict__ norms) {
     double m[4] = {0.0, 0.0, 0.0, 0.0};
     for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        m[0] = fmax(m[0], fabs(r[i])); m[1] = fmax(m[1], colsum[i]); m[2] = fmax(m[2], fabs(x[i])); m[3] = fmax(m[3], fabs(b[i]));
+        m[0] = resid_max(m[0], fabs(r[i])); m[1] = resid_max(m[1], colsum[i]); m[2] = resid_max(m[2], fabs(x[i]));
+        m[3] = resid_max(m[3], fabs(b[i]));
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         double v = m[k];
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
+        for (int off = 32; off > 0; off >>= 1) v = resid_max(v, __shfl_down(v, off, 64));
         if ((threadIdx.x & 63) == 0) atomicMax(norms + k, (unsigned long long)__double_as_longlong(v));
     }
 }

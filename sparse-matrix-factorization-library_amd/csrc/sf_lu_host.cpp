@@ -14,6 +14,7 @@
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <time.h>
 #include <unordered_map>
@@ -375,13 +376,16 @@ int SparseFrame_validate(struct matrix_info_struct* mi) {   // L:3702-3858
         }
     }
     double anorm = 0, bnorm = 0, xnorm = 0, rnorm = 0;
+    bool finite = true;     // fmax returns its non-NaN operand: a non-finite r_i or x_i is kept apart, as k_refine_norms' flag word does
     for (sf_long i = 0; i < n; ++i) {
         anorm = std::fmax(anorm, colsum[i]);
         bnorm = std::fmax(bnorm, std::fabs(mi->Bx[i]));
         xnorm = std::fmax(xnorm, std::fabs(mi->Xx[i]));
         rnorm = std::fmax(rnorm, std::fabs(mi->Rx[i]));
+        if (!std::isfinite(mi->Rx[i]) || !std::isfinite(mi->Xx[i])) finite = false;
     }
-    mi->residual = rnorm / (anorm * xnorm + bnorm);
+    // a non-finite solution is no solve at all: NaN fails every `residual <= tol` (the return code stays 0)
+    mi->residual = finite ? rnorm / (anorm * xnorm + bnorm) : std::numeric_limits<double>::quiet_NaN();
     return 0;
 }
 

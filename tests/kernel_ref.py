@@ -20,6 +20,8 @@ it back).  Each region is surrounded by guard bands of GUARD doubles (64 KiB) ho
 a kernel's documented read footprint hold NaN too, so a read that leaks into a stored result shows up as a non-finite
 value; every element outside the documented write footprint is compared bit for bit with its value before the launch.
 """
+import types
+
 import numpy as np
 
 LD = np.longdouble
@@ -548,3 +550,389 @@ def logdet_bound(logs):
     mag = np.sum(np.abs(np.asarray(logs, dtype=LD)))
     nparts = (len(logs) + 255) // 256
     return (SAFETY * (8 + (nparts + 255) // 256 + 2) + 1) * U * mag
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# residual, refinement, reductions, sampling and transfers, one launch at a time: tests/test_kernels_apply.py
+# (csrc/sf_kernels.hip: k_resid_*, k_loadmap_drop; sf_refine.hip; sf_gram.hip, sf_gram_lu.hip; sf_sample.hip; sf_device_io.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+GRID_CAP = 1024              # workgroups of the strided launches (QF_MAXB, DIO_MAXB, the norms launches, k_loadmap_drop)
+GRAM_SLAB_ROWS, GRAM_MAX_SLABS, GRAM_STRETCH, SVM_W = 2048, 256, 64, 16
+# every single fault the emulations below can inject; tests/test_kernels_apply.py shows for each that a checker rejects it
+APPLY_FAULTS = ("dropped tail group", "slab overlap", "wave offset", "no mirror", "padding written", "inverse perm", "ld is n", "no stride",
+                "duplicate summed", "pos from direct", "nan dropped", "map -1 read", "best overwritten")
+
+
+def nan_max(a):
+    """the maximum that keeps a NaN (np.max does; np.fmax.reduce is the parent's NaN-dropping one)"""
+    a = np.asarray(a, dtype=np.float64)
+    return float(np.max(a)) if a.size else 0.0
+
+
+def strided_visit(n, per_group, fault=None):
+    """(nb, passes): workgroups of a launch that caps its grid at GRID_CAP and strides over the rest, per_group elements per workgroup
+    and pass.  "no stride": every workgroup makes one pass only, so elements past GRID_CAP * per_group are never visited."""
+    nb = min(GRID_CAP, -(-n // per_group))
+    passes = -(-n // (nb * per_group))
+    return nb, (1 if fault == "no stride" else passes)
+
+
+# ---- launch_residual ----
+def resid_ref(n, Lp, Li, Lx, Up, Ui, Ux, x):
+    """longdouble r = A x - b with b_i = 1 + i / n, per row: mag = sum |a_ij| |x_j| + |b_i| and cnt = the entries of the row;
+    colsum = the column sums of |A|.  Up None: (Lp, Li, Lx) is one triangle used symmetrically; else L by column and U by row (its
+    diagonal entries skipped: the L part holds the diagonal)."""
+    b = 1.0 + np.arange(n, dtype=np.float64) / np.float64(n)
+    rows, cols, vals = [np.asarray(Li, dtype=np.int64)], [np.repeat(np.arange(n), np.diff(Lp))], [np.asarray(Lx, dtype=np.float64)]
+    if Up is None:
+        off = rows[0] != cols[0]
+        rows.append(cols[0][off]); cols.append(rows[0][off]); vals.append(vals[0][off])
+    else:
+        ur, uc = np.repeat(np.arange(n), np.diff(Up)), np.asarray(Ui, dtype=np.int64)
+        off = ur != uc
+        rows.append(ur[off]); cols.append(uc[off]); vals.append(np.asarray(Ux, dtype=np.float64)[off])
+    rows, cols, vals = np.concatenate(rows), np.concatenate(cols), np.concatenate(vals).astype(LD)
+    xl = np.asarray(x, dtype=LD)
+    r, mag, colsum = -b.astype(LD), np.abs(b).astype(LD), np.zeros(n, dtype=LD)
+    np.add.at(r, rows, vals * xl[cols])
+    np.add.at(mag, rows, np.abs(vals) * np.abs(xl[cols]))
+    np.add.at(colsum, cols, np.abs(vals))
+    cnt = np.bincount(rows, minlength=n)
+    ccnt = np.bincount(cols, minlength=n)
+    return types.SimpleNamespace(b=b, r=r, mag=mag, colsum=colsum, cnt=cnt, ccnt=ccnt)
+
+
+def resid_norms_emulate(r, colsum, x, b, fault=None):
+    """the four maxima as k_resid_norms takes them.  "nan dropped": fmax, which returns its non-NaN operand -- the parent's maximum,
+    the fault that the NaN-keeping maximum of k_resid_norms fixes; "no stride": nothing past GRID_CAP * 256 elements is visited"""
+    n = len(r)
+    nb, passes = strided_visit(n, 256, fault)
+    lim = min(n, nb * 256 * passes)
+    red = (lambda a: float(np.fmax.reduce(a, initial=0.0))) if fault == "nan dropped" else nan_max
+    return np.array([red(np.abs(r[:lim])), red(colsum[:lim]), red(np.abs(x[:lim])), red(np.abs(b[:lim]))])
+
+
+def resid_norms_check(norms, r, colsum, x, b, what):
+    """norms[k] = the maximum of the launch's OWN r, colsum, x, b, bit for bit (a maximum does not round); a NaN among them is kept.
+    Returns the residual formed from norms[] as sf_chol_plan_validate forms it."""
+    for k, a in enumerate((np.abs(r), colsum, np.abs(x), np.abs(b))):
+        want = nan_max(a)
+        if np.isnan(want):
+            if not np.isnan(norms[k]):
+                raise AssertionError(f"{what}: norms[{k}] = {norms[k]!r} is beyond the bound: a NaN among its inputs was dropped")
+        elif bits(np.array([norms[k]]))[0] != bits(np.array([want]))[0]:
+            raise AssertionError(f"{what}: norms[{k}] = {norms[k]!r} is beyond the bound: the maximum is {want!r}")
+    with np.errstate(invalid="ignore"):
+        res = norms[0] / (norms[1] * norms[2] + norms[3])
+    if not (np.all(np.isfinite(r)) and np.all(np.isfinite(x))) and not np.isnan(res):
+        raise AssertionError(f"{what}: a non-finite r or x gives the residual {res!r}, not NaN")
+    return res
+
+
+def resid_check(ref, r, colsum, b, what):
+    """r and colsum per element: the launch sums with floating-point atomics, so the order is free -- per row the depth is (entries
+    of the row + 1) (every product and b_i enter one chain in the worst order) on mag = sum |a_ij| |x_j| + |b_i|; colsum likewise
+    with the entries of the column.  b_i = 1 + i / n bit for bit.  Returns the worst err / bound."""
+    if np.any(bits(b) != bits(ref.b)):
+        raise AssertionError(f"{what}: b is beyond the bound: not 1 + i / n bit for bit at {np.flatnonzero(bits(b) != bits(ref.b))[:8].tolist()}")
+    w1 = within_ratio(r, ref.r, SAFETY * (ref.cnt + 1) * U * ref.mag, what + " r")
+    w2 = within_ratio(colsum, ref.colsum, SAFETY * np.maximum(ref.ccnt, 1) * U * ref.colsum, what + " colsum")
+    return max(w1, w2)
+
+
+# ---- launch_refine_resid / _abs_sums / _norms ----
+RF_G = 8
+
+
+def refine_emulate(ptr, col, pos, Vd, Vt, x, b, fault=None):
+    """float64 emulation of k_refine_resid<false>: lane g of a row takes the entries g, g + 8, ... with fma, then xor 4, 2, 1.
+    "duplicate summed": the slot after a row's first entry (a superseded duplicate, left out of the form) is summed too;
+    "pos from direct": ~pos read from the direct array.  Returns (r, w)."""
+    n = len(ptr) - 1
+    r, w = np.empty(n), np.empty(n)
+    for i in range(n):
+        lanes, mags = np.zeros(RF_G), np.zeros(RF_G)
+        for k, e in enumerate(range(ptr[i], ptr[i + 1])):
+            ps = int(pos[e])
+            a = Vd[ps] if ps >= 0 else (Vd[~ps] if fault == "pos from direct" else Vt[~ps])
+            if fault == "duplicate summed" and k == 0:
+                a = a + (Vd[ps + 1] if ps >= 0 else Vt[~ps + 1])
+            lanes[k % RF_G] += a * x[col[e]]
+            mags[k % RF_G] += abs(a) * abs(x[col[e]])
+        for m in (4, 2, 1):
+            lanes, mags = lanes + lanes[np.arange(RF_G) ^ m], mags + mags[np.arange(RF_G) ^ m]
+        r[i], w[i] = b[i] - lanes[0], mags[0] + abs(b[i])
+    return r, w
+
+
+def refine_ref(ptr, col, pos, Vd, Vt, x, b):
+    """longdouble (r, w, sums, depth): r = b - A x, w = |A| |x| + |b|, sums = the rows' sums of |a|; depth = the longest chain of
+    additions of a row: ceil(len / 8) lane-serial fma steps, 3 xor steps, the subtraction from b_i"""
+    n = len(ptr) - 1
+    pos = np.asarray(pos, dtype=np.int64)
+    a = np.where(pos >= 0, np.asarray(Vd)[np.maximum(pos, 0)], np.asarray(Vt)[np.maximum(~pos, 0)]).astype(LD) if len(pos) else np.zeros(0, dtype=LD)
+    rows = np.repeat(np.arange(n), np.diff(ptr))
+    xl = np.asarray(x, dtype=LD)[np.asarray(col[:len(pos)], dtype=np.int64)] if len(pos) else np.zeros(0, dtype=LD)
+    ax, mag, sums = np.zeros(n, dtype=LD), np.zeros(n, dtype=LD), np.zeros(n, dtype=LD)
+    np.add.at(ax, rows, a * xl)
+    np.add.at(mag, rows, np.abs(a) * np.abs(xl))
+    np.add.at(sums, rows, np.abs(a))
+    bl = np.asarray(b, dtype=LD)
+    depth = -(-np.diff(ptr) // RF_G) + 3 + 1
+    return bl - ax, mag + np.abs(bl), sums, depth
+
+
+def refine_check(ref, r, w, what):
+    rr, ww, _, depth = ref
+    bound = SAFETY * depth * U * ww
+    return max(within_ratio(r, rr, bound, what + " r"), within_ratio(w, ww, bound, what + " w"))
+
+
+def refine_norms_ref(r, w, x, b, info):
+    """the five words k_refine_norms leaves in zeroed words: maxima that drop a NaN (they are bit patterns merged by an integer
+    maximum; a maximum of 0 is never written), the flag word as an integer"""
+    r, x, b = np.abs(r), np.abs(x), np.abs(b)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q = np.where(w > 0, r / np.where(w > 0, w, 1.0), 0.0)
+    fm = lambda a: float(np.fmax.reduce(a, initial=0.0))
+    bad = not (np.all(np.isfinite(r)) and np.all(np.isfinite(x)) and np.all(np.isfinite(b)))
+    return np.array([fm(q), fm(r), fm(x), fm(b)]), int(bad) | (2 if info else 0)
+
+
+def refine_norms_emulate(r, w, x, b, info, s0, fault=None):
+    """k_refine_norms on the five words s0 (four doubles and the flag word as an integer): workgroups stride over the rows; a maximum
+    is merged into its word only when it is > 0 (integer maximum of the bit patterns of non-negative doubles).  "no stride": nothing
+    past GRID_CAP * 256 rows is visited.  Returns (words, flags)."""
+    n = len(r)
+    nb, passes = strided_visit(n, 256, fault)
+    lim = min(n, nb * 256 * passes)
+    m, flags = refine_norms_ref(r[:lim], w[:lim], x[:lim], b[:lim], info)
+    out = np.array(s0[0], dtype=np.float64)
+    for k in range(4):
+        if m[k] > 0 and bits(m[k:k + 1])[0] > bits(out[k:k + 1])[0]:
+            out[k] = m[k]
+    return out, int(s0[1]) | flags
+
+
+def refine_update_emulate(x, d, best, save, fault=None):
+    """k_refine_update: best <- x when save, then x += d.  "best overwritten": best is written although save == 0"""
+    if save or fault == "best overwritten":
+        best[:len(x)] = x
+    x += d
+    return x, best
+
+
+def gather_values_emulate(Ax, map_, out, fault=None):
+    """k_dev_gather_values: out[p] = Ax[map[p]], 0.0 where map[p] < 0.  "map -1 read": the entry -1 is used as an index"""
+    m = np.asarray(map_)
+    out[:len(m)] = Ax[m] if fault == "map -1 read" else np.where(m >= 0, Ax[np.maximum(m, 0)], 0.0)
+    return out
+
+
+# ---- the fixed-order sums: launch_dot, launch_quadform ----
+def two_pass_sum(terms, W, fault=None):
+    """float64 emulation of k_dot_part / _final (W = 1, terms = x_i y_i) and k_quadform_part / _final<W> (terms = the row-major
+    n x W block of squares): G = 256 / W row groups per workgroup, nb = min(GRID_CAP, ceil(n / G)) workgroups striding over the rows
+    serially, a tree over the groups, then one workgroup over the nb parts in the same way.  Returns the W sums."""
+    def tree(v):                # v: (..., G, W)
+        while v.shape[-2] > 1:
+            h = v.shape[-2] // 2
+            v = v[..., :h, :] + v[..., h:, :]
+        return v[..., 0, :]
+    terms = np.asarray(terms, dtype=np.float64).reshape(-1, W)
+    n, G = terms.shape[0], 256 // W
+    nb, passes = strided_visit(n, G, fault)
+    pad = np.zeros((nb * G * passes, W))
+    lim = min(n, len(pad))
+    pad[:lim] = terms[:lim]
+    v = np.zeros((nb, G, W))
+    for t in pad.reshape(passes, nb, G, W):
+        v = v + t
+    part = tree(v)                                       # nb x W
+    p2 = -(-nb // G)
+    pad2 = np.zeros((p2 * G, W))
+    pad2[:nb] = part
+    v = np.zeros((G, W))
+    for t in pad2.reshape(p2, G, W):
+        v = v + t
+    return tree(v)
+
+
+def two_pass_depth(n, W):
+    """the longest chain of additions behind one result of two_pass_sum: the products' own rounding (1), ceil(n / (nb G)) serial
+    steps, log2(G) tree levels; then ceil(nb / G) serial steps and the same tree"""
+    G = 256 // W
+    nb, passes = strided_visit(n, G)
+    lv = G.bit_length() - 1
+    return 1 + passes + lv + -(-nb // G) + lv
+
+
+def sum_check(got, terms, W, what):
+    """got (W sums) against the longdouble column sums of `terms` (n x W) within SAFETY depth u sum |terms|"""
+    t = np.asarray(terms, dtype=LD).reshape(-1, W)
+    return within_ratio(np.asarray(got), t.sum(axis=0), SAFETY * two_pass_depth(t.shape[0], W) * U * np.abs(t).sum(axis=0), what)
+
+
+# ---- the Gram reductions: launch_gram_row, launch_gram2_col ----
+def gram_slabs(n):
+    """(ns, slab_rows) as sf::gram_slabs cuts the rows"""
+    want = min(GRAM_MAX_SLABS, max(1, -(-n // GRAM_SLAB_ROWS)))
+    rows = -(-(-(-n // want)) // GRAM_STRETCH) * GRAM_STRETCH
+    return -(-n // rows), rows
+
+
+def gram_depth(n):
+    """the longest chain of additions behind one entry of G: a slab has slab_rows / 64 stretches, an accumulator chain takes one
+    four-row group of each (4 products per MFMA: slab_rows / 16 additions), the four chains are added pairwise (2), the four
+    waves in order (3), the ns slabs in order (ns), and each product rounds once (1)"""
+    ns, rows = gram_slabs(n)
+    return rows // 16 + 2 + 3 + ns + 1
+
+
+def gram_tile_emulate(Ya, Yb, fault=None):
+    """float64 emulation of one 16 x 16 tile Ya^T Yb (n x 16 each) in the kernels' order: slab by slab; in a slab wave w and chain u
+    take the four-row groups at 4 w + 16 u of every 64-row stretch.  Faults: the last partial four-row group of a slab dropped; the
+    first row of the next slab counted in both; wave 1's groups one stretch late (its first stretch is never read)."""
+    n = Ya.shape[0]
+    ns, rows = gram_slabs(n)
+    out = np.zeros((SVM_W, SVM_W))
+    for s in range(ns):
+        r0, r1 = s * rows, min(n, (s + 1) * rows)
+        if fault == "slab overlap" and r1 < n:
+            r1 += 1
+        if fault == "dropped tail group":
+            r1 -= (r1 - r0) % 4
+        A, B = np.zeros((-(-(r1 - r0) // 64) * 64, SVM_W)), np.zeros((-(-(r1 - r0) // 64) * 64, SVM_W))
+        A[:r1 - r0], B[:r1 - r0] = Ya[r0:r1], Yb[r0:r1]
+        A, B = A.reshape(-1, 4, 4, 4, SVM_W), B.reshape(-1, 4, 4, 4, SVM_W)          # stretch, chain u, wave w, row of the group
+        if fault == "wave offset":
+            A = A.copy()
+            A[0, :, 1] = 0.0
+        acc = np.zeros((4, 4, SVM_W, SVM_W))
+        for t in range(A.shape[0]):
+            acc = acc + np.einsum("uwqi,uwqj->uwij", A[t], B[t])
+        wave = (acc[0] + acc[1]) + (acc[2] + acc[3])
+        part = wave[0]
+        for w in range(1, 4):
+            part = part + wave[w]
+        out = out + part
+    return out
+
+
+def gram_row_emulate(Y, n, a, k, G, fault=None):
+    """launch_gram_row on the chunks Y[0 .. a] (each n x 16) into the column-major k x k G (a 2-D array, G[i, j], any leading
+    dimension >= k): the tiles (a, b <= a) and their mirrors; a diagonal tile mirrors its lower triangle from one value.
+    Faults: an off-diagonal tile's mirror not written; the indices >= k written."""
+    for b in range(a + 1):
+        T = gram_tile_emulate(Y[a], Y[b], fault)
+        for i in range(SVM_W):
+            for j in range(SVM_W):
+                gi, gj = a * SVM_W + i, b * SVM_W + j
+                lim = G.shape[0] if fault == "padding written" else k
+                if gi >= lim or gj >= lim or gj >= G.shape[1] or (a == b and i < j):
+                    continue
+                G[gi, gj] = T[i, j]
+                if gi != gj and not (fault == "no mirror" and a != b) and gi < G.shape[1]:
+                    G[gj, gi] = T[i, j]
+    return G
+
+
+def gram2_col_emulate(Z, Yb, n, b, m, k, G, fault=None):
+    """launch_gram2_col: the tiles (a < nza, b) of Z^T Y into the column-major m x k G; nothing mirrored"""
+    for a in range(len(Z)):
+        T = gram_tile_emulate(Z[a], Yb, fault)
+        for i in range(SVM_W):
+            for j in range(SVM_W):
+                gi, gj = a * SVM_W + i, b * SVM_W + j
+                if fault == "padding written":
+                    if gi < G.shape[0] and gj < G.shape[1]:
+                        G[gi, gj] = T[i, j]
+                elif gi < m and gj < k:
+                    G[gi, gj] = T[i, j]
+    return G
+
+
+def gram_check(G0, G1, Zc, Yc, n, rows_of, cols_of, m, k, mirror, what):
+    """G1 (after) against G0 (before), both 2-D [row, column] views with the padding of the leading dimension as extra rows.
+    Written: entry (16 a + i, 16 b + j) for the (a, b) tiles of the launch -- rows_of / cols_of = the chunk indices, Zc[a] / Yc[b] the
+    n x 16 chunks -- with row < m and column < k; mirror: also the transposed entry, and the two must agree bit for bit.
+    Each against the longdouble sum within SAFETY gram_depth(n) u sum |terms|; everything else bit-identical.  Returns the worst ratio."""
+    written = np.zeros(G0.shape, dtype=bool)
+    worst = 0.0
+    depth = gram_depth(n)
+    for a in rows_of:
+        for b in cols_of(a):
+            ref = matmul_ld(np.asarray(Zc[a]).T, Yc[b])
+            bound = SAFETY * depth * U * matmul_ld(np.abs(np.asarray(Zc[a])).T, np.abs(Yc[b]))
+            ni, nj = max(0, min(SVM_W, m - a * SVM_W)), max(0, min(SVM_W, k - b * SVM_W))
+            got = G1[a * SVM_W:a * SVM_W + ni, b * SVM_W:b * SVM_W + nj]
+            written[a * SVM_W:a * SVM_W + ni, b * SVM_W:b * SVM_W + nj] = True
+            worst = max(worst, within_ratio(got, ref[:ni, :nj], bound[:ni, :nj], f"{what} tile ({a}, {b})"))
+            if mirror:
+                written[b * SVM_W:b * SVM_W + nj, a * SVM_W:a * SVM_W + ni] = True
+                back = G1[b * SVM_W:b * SVM_W + nj, a * SVM_W:a * SVM_W + ni].T
+                if np.any(bits(back) != bits(np.ascontiguousarray(got))):
+                    raise AssertionError(f"{what} tile ({a}, {b}): beyond the bound: the mirror differs from the tile")
+    assert_unchanged(G0, G1, written, what)
+    return worst
+
+
+# ---- the transfers of sf_device_io.hip ----
+def _perm_index(perm, n, fault):
+    if perm is None:
+        return np.arange(n)
+    return np.argsort(perm) if fault == "inverse perm" else np.asarray(perm)
+
+
+def load1_emulate(B, perm, n, x, fault=None):
+    x[:n] = B[_perm_index(perm, n, fault)]
+    return x
+
+
+def store1_emulate(x, perm, n, X, fault=None):
+    X[_perm_index(perm, n, fault)] = x[:n]
+    return X
+
+
+def pack_emulate(B, ldb, perm, n, cw, X, fault=None):
+    """X (flat, row-major n x 16 in front) from the column-major chunk B (flat, leading dimension ldb); columns >= cw zero"""
+    src = _perm_index(perm, n, fault)
+    ld = n if fault == "ld is n" else ldb
+    blk = np.zeros((n, SVM_W))
+    for c in range(cw):
+        blk[:, c] = B[src + c * ld]
+    if fault == "padding written" and cw < SVM_W:
+        blk[:, cw] = B[src]
+    X[:n * SVM_W] = blk.ravel()
+    return X
+
+
+def unpack_emulate(X, perm, n, cw, D, ldx, fault=None):
+    dst = _perm_index(perm, n, fault)
+    ld = n if fault == "ld is n" else ldx
+    blk = X[:n * SVM_W].reshape(n, SVM_W)
+    for c in range(cw + (1 if fault == "padding written" and cw < SVM_W else 0)):
+        D[dst + c * ld] = blk[:, c]
+    return D
+
+
+def assert_bits(got, want, what):
+    bad = bits(np.asarray(got, dtype=np.float64)) != bits(np.asarray(want, dtype=np.float64))
+    if bad.any():
+        raise AssertionError(f"{what}: {int(bad.sum())} elements are beyond the bound (bit for bit), first at {np.argwhere(bad)[:8].tolist()}")
+
+
+def absmax_emulate(v, fault=None):
+    """the parts of k_dev_absmax: workgroup blk strides over v; fmax drops a NaN, as documented"""
+    n = len(v)
+    nb, passes = strided_visit(n, 256, fault)
+    pad = np.zeros(nb * 256 * passes)
+    lim = min(n, len(pad))
+    pad[:lim] = np.abs(v[:lim])
+    return np.fmax.reduce(pad.reshape(passes, nb, 256), axis=(0, 2), initial=0.0)
+
+
+def loadmap_drop_emulate(drop, map_, fault=None):
+    nb, passes = strided_visit(len(drop), 256, fault)
+    map_[drop[:nb * 256 * passes]] = -1
+    return map_

@@ -590,4 +590,186 @@ int kp_lu_selinv_pack(const KpSel* sel, const int64_t* RefXp, const double* SL, 
     return (int)d.rc;
 }
 
+// ---- residual, refinement, reductions, sampling and transfers (sf_kernels.hip, sf_refine.hip, sf_gram.hip, sf_gram_lu.hip,
+// sf_sample.hip, sf_device_io.hip): tests/test_kernels_apply.py ----
+// Every double operand lies at an offset of ONE image `buf` (in and out), so that a test sees everything a launch wrote.
+
+// Up null: (Lp, Li) is one triangle used symmetrically.  Values at buf + lx_off / ux_off; r, colsum, b: n doubles each, norms: 4
+int kp_residual(const int64_t* Lp, const int32_t* Li, int64_t nnzL, const int64_t* Up, const int32_t* Ui, int64_t nnzU, int32_t n, double* buf,
+                int64_t nbuf, int64_t lx_off, int64_t ux_off, int64_t x_off, int64_t r_off, int64_t c_off, int64_t b_off, int64_t norms_off) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    const int64_t* dLp = d.in(Lp, (int64_t)n + 1);
+    const int32_t* dLi = d.in(Li, nnzL);
+    const int64_t* dUp = Up ? d.in(Up, (int64_t)n + 1) : nullptr;
+    const int32_t* dUi = Up ? d.in(Ui, nnzU) : nullptr;
+    if (d.rc == hipSuccess)
+        sf::launch_residual(dLp, dLi, W + lx_off, dUp, dUi, Up ? W + ux_off : nullptr, n, W + x_off, W + r_off, W + c_off, W + b_off,
+                            W + norms_off, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+int kp_loadmap_drop(const int64_t* drop, int64_t count, int64_t* map, int64_t nmap) {
+    Dev d;
+    const int64_t* D = d.in(drop, count);
+    int64_t* M = d.in(map, nmap);
+    if (d.rc == hipSuccess) sf::launch_loadmap_drop(D, count, M, 0);
+    d.finish();
+    d.out(map, M, nmap);
+    return (int)d.rc;
+}
+
+// the form's arrays: n + 1 pointers, nent entries; Vd / Vt at buf + vd_off / vt_off.  sums == 0: launch_refine_resid (x, b, r, w);
+// otherwise launch_refine_abs_sums into the word at buf + amax_off
+int kp_refine_resid(const int64_t* ptr, const int32_t* col, const int64_t* pos, int64_t nent, int64_t n, double* buf, int64_t nbuf,
+                    int64_t vd_off, int64_t vt_off, int64_t x_off, int64_t b_off, int64_t r_off, int64_t w_off, int sums, int64_t amax_off) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    sf::RefineForm f;
+    f.ptr = d.in(ptr, n + 1);
+    f.col = d.in(col, nent);
+    f.pos = d.in(pos, nent);
+    f.Vd = W + vd_off;
+    f.Vt = W + vt_off;
+    if (d.rc == hipSuccess) {
+        if (sums) sf::launch_refine_abs_sums(f, n, W + amax_off, 0);
+        else sf::launch_refine_resid(f, n, W + x_off, W + b_off, W + r_off, W + w_off, 0);
+    }
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+// use_info == 0: no info word (null)
+int kp_refine_norms(int64_t n, double* buf, int64_t nbuf, int64_t r_off, int64_t w_off, int64_t x_off, int64_t b_off, int64_t s_off,
+                    int use_info, int solve_info_value) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    const int* I = use_info ? d.in(&solve_info_value, 1) : nullptr;
+    if (d.rc == hipSuccess) sf::launch_refine_norms(n, W + r_off, W + w_off, W + x_off, W + b_off, I, W + s_off, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+int kp_refine_update(int64_t n, double* buf, int64_t nbuf, int64_t x_off, int64_t d_off, int64_t best_off, int save) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    if (d.rc == hipSuccess) sf::launch_refine_update(n, W + x_off, W + d_off, W + best_off, save, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+int kp_gram_slabs(int64_t n, int64_t* slab_rows) { return sf::gram_slabs(n, slab_rows); }
+
+int kp_gram_row(double* buf, int64_t nbuf, int64_t y_off, int64_t n, int a, int64_t k, int64_t part_off, int64_t g_off, int64_t ldg) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    if (d.rc == hipSuccess) sf::launch_gram_row(W + y_off, n, a, k, W + part_off, W + g_off, ldg, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+int kp_gram2_col(double* buf, int64_t nbuf, int64_t z_off, int64_t yb_off, int64_t n, int nza, int b, int64_t m, int64_t k, int64_t part_off,
+                 int64_t g_off, int64_t ldg) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    if (d.rc == hipSuccess) sf::launch_gram2_col(W + z_off, W + yb_off, n, nza, b, m, k, W + part_off, W + g_off, ldg, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+int kp_dot(double* buf, int64_t nbuf, int64_t x_off, int64_t y_off, int64_t n, int64_t scratch_off, int64_t out_off) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    if (d.rc == hipSuccess) sf::launch_dot(W + x_off, W + y_off, n, W + scratch_off, W + out_off, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+int kp_quadform(double* buf, int64_t nbuf, int64_t x_off, int64_t n, int width, int64_t scratch_off) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    if (d.rc == hipSuccess) sf::launch_quadform(W + x_off, n, width, W + scratch_off, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+int kp_sample_fill(double* buf, int64_t nbuf, int64_t x_off, int64_t n, int cw, uint64_t seed, uint64_t s0) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    if (d.rc == hipSuccess) sf::launch_sample_fill(W + x_off, n, cw, seed, s0, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+// perm: n entries, or null
+int kp_dev_load1(double* buf, int64_t nbuf, int64_t b_off, const int32_t* perm, int64_t n, int64_t x_off) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    const int32_t* P = perm ? d.in(perm, n) : nullptr;
+    if (d.rc == hipSuccess) sf::launch_dev_load1(W + b_off, P, n, W + x_off, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+int kp_dev_store1(double* buf, int64_t nbuf, int64_t x_off, const int32_t* perm, int64_t n, int64_t out_off) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    const int32_t* P = perm ? d.in(perm, n) : nullptr;
+    if (d.rc == hipSuccess) sf::launch_dev_store1(W + x_off, P, n, W + out_off, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+int kp_dev_pack(double* buf, int64_t nbuf, int64_t b_off, int64_t ldb, const int32_t* perm, int64_t n, int cw, int64_t x_off) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    const int32_t* P = perm ? d.in(perm, n) : nullptr;
+    if (d.rc == hipSuccess) sf::launch_dev_pack(W + b_off, ldb, P, n, cw, W + x_off, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+int kp_dev_unpack(double* buf, int64_t nbuf, int64_t x_off, const int32_t* perm, int64_t n, int cw, int64_t d_off, int64_t ldx) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    const int32_t* P = perm ? d.in(perm, n) : nullptr;
+    if (d.rc == hipSuccess) sf::launch_dev_unpack(W + x_off, P, n, cw, W + d_off, ldx, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+int kp_dev_gather_values(double* buf, int64_t nbuf, int64_t ax_off, const int64_t* map, int64_t count, int64_t out_off) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    const int64_t* M = d.in(map, count);
+    if (d.rc == hipSuccess) sf::launch_dev_gather_values(W + ax_off, M, count, W + out_off, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+// *nparts = the launcher's return value: the parts written at buf + part_off
+int kp_dev_absmax(double* buf, int64_t nbuf, int64_t v_off, int64_t count, int64_t part_off, int* nparts) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    if (d.rc == hipSuccess) *nparts = sf::launch_dev_absmax(W + v_off, count, W + part_off, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
 }  // extern "C"

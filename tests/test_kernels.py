@@ -58,7 +58,10 @@ def test_probe_compiles(tmp_path):
     for name in ("kp_gemm", "kp_update_small", "kp_potrf", "kp_getrf", "kp_trsm", "kp_step", "kp_build_loadmap", "kp_solve_fwd",
                  "kp_solve_bwd", "kp_pack_lu", "kp_lu_fill_u11", "kp_factor_hash", "kp_tsolve_bwd", "kp_condest_fill", "kp_condest_sign_norm",
                  "kp_condest_argmax_next", "kp_solve_many_pack", "kp_solve_many_unpack", "kp_selinv_small", "kp_lu_selinv_small",
-                 "kp_selinv_trinv", "kp_selinv_gemm", "kp_selinv_sum", "kp_selinv_finish", "kp_selinv_diag", "kp_logdet", "kp_lu_selinv_pack"):
+                 "kp_selinv_trinv", "kp_selinv_gemm", "kp_selinv_sum", "kp_selinv_finish", "kp_selinv_diag", "kp_logdet", "kp_lu_selinv_pack",
+                 "kp_residual", "kp_loadmap_drop", "kp_refine_resid", "kp_refine_norms", "kp_refine_update", "kp_gram_slabs", "kp_gram_row",
+                 "kp_gram2_col", "kp_dot", "kp_quadform", "kp_sample_fill", "kp_dev_load1", "kp_dev_store1", "kp_dev_pack", "kp_dev_unpack",
+                 "kp_dev_gather_values", "kp_dev_absmax"):
         assert f" T {name}" in nm
 
 
