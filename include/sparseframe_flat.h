@@ -147,6 +147,37 @@ int sf_chol_plan_get_selinv_range(sf_chol_plan *plan, sf_long e_begin, sf_long e
 int sf_chol_plan_selinv_diag(sf_chol_plan *plan, sf_float *d);
 /* log det A = 2 sum_j log L_jj of the resident factor, reduced on the device in a fixed order (independent of selinv) */
 int sf_chol_plan_logdet(sf_chol_plan *plan, sf_float *out);
+/* ---- Sigma read where the caller wants it: on the pattern the plan was created with, as tr(Sigma M(V)), and at
+ * (row, column) pairs.  Gathers and fixed-order reductions over the arena of sf_chol_plan_selinv; everything in permuted space, as
+ * sf_chol_plan_get_selinv_range.  All of them need what sf_chol_plan_selinv needs AND a valid arena (stat "selinv_valid" == 1):
+ * otherwise -- schedule-only, partial, sharded, mapped, out-of-core and LU plans, no or a stale arena -- SF_ERR_ARG with every output
+ * untouched; so are NULL pointers, negative counts and a short leading dimension.  Device state (the position of every entry, the
+ * parts of a trace, the staging buffer of the pairs) is allocated by the first call that needs it and kept until destroy: stat
+ * "bytes_selinv_pattern", not in "bytes_device"; SF_ERR_ALLOC leaves the plan usable.  "last_selinv_pattern_ms": device time of the
+ * last call's kernels, copies excluded. ---- */
+/* out[p] = Sigma(Li[p], j) for EVERY position p of column j of the structure the plan was created with (Lp / Li), nnz doubles --
+ * also where the assembly ignores the position: an entry given again later in its column gets the Sigma of its (i, j) all the same */
+int sf_chol_plan_selinv_values(sf_chol_plan *plan, sf_float *out /* nnz */);
+/* the same into device memory of the plan's device (checked as sf_chol_plan_solve_device checks its blocks) */
+int sf_chol_plan_selinv_values_device(sf_chol_plan *plan, sf_float *d_out /* nnz */);
+#define SF_SEL_MAPPED 1      /* V is in the caller's own layout and read through the map of sf_chol_plan_set_value_map */
+#define SF_SEL_MAX_M 64
+/* out[t] = tr(Sigma M(V_t)), t < m, where M(V_t) is the matrix sf_chol_plan_set_values(V_t) would assemble (positions the assembly
+ * ignores do not count, their V is never read): sum over the diagonal entries of Sigma_jj V_jj plus twice the sum over the others
+ * of Sigma_ij V_ij -- for V = dA/dtheta the derivative of log det A.  V: column-major, column t = V + t ldv, nnz doubles each, ldv >=
+ * max(nnz, 1); with SF_SEL_MAPPED column t has nsrc doubles in the caller's layout (a -1 map entry counts as 0), ldv >= max(nsrc, 1),
+ * and a plan without a stored map is refused.  0 <= m <= SF_SEL_MAX_M; m == 0: SF_OK, nothing written.  One pass over the load map
+ * and the arena whatever m is, no floating-point atomics; the order of every sum is a function of nnz alone, so the same arena and
+ * V give the same bits every time, and out[t] depends on column t of V only (a NaN there reaches out[t] and nothing else). */
+int sf_chol_plan_selinv_trace(sf_chol_plan *plan, sf_long m, const sf_float *V, sf_long ldv, int flags /* 0 | SF_SEL_MAPPED */,
+                              sf_float *out /* m */);
+int sf_chol_plan_selinv_trace_device(sf_chol_plan *plan, sf_long m, const sf_float *dV, sf_long ldv, int flags, sf_float *d_out /* m */);
+/* out[k] = Sigma(rows[k], cols[k]), permuted indices, either triangle; found on the device by the search of the assembly (the
+ * column's supernode, then its row list).  A pair outside the pattern of L gets a quiet NaN and is counted in *outside (may be
+ * NULL; also stat "last_selinv_outside") -- the call still returns SF_OK.  An index outside [0, n): SF_ERR_ARG before anything is
+ * written.  The pairs go up in chunks of 65536 (stat "selinv_entries_chunk"). */
+int sf_chol_plan_selinv_entries(sf_chol_plan *plan, sf_long count, const sf_long *rows, const sf_long *cols, sf_float *out,
+                                sf_long *outside /* or NULL */);
 /* SparseFrame_validate on the device (C:3141-3266; LU plans: L:3702-3858): b_i = 1 + i/n, solve with the resident factor,
  * r = A x - b from the plan's copy of the matrix values, *residual = |r|_inf / (|A|_1 |x|_inf + |b|_inf).  x_host may be NULL.
  * *residual is NaN when any r_i or x_i is not finite (NaN fails every `<=`); the return code is SF_OK all the same.  The struct
@@ -594,6 +625,27 @@ int sf_lu_plan_selinv_diag(sf_lu_plan *plan, sf_float *d);
  * same plan kinds.  Needs a successful factorization of the current values.  In permuted space, which has the determinant of the
  * caller's matrix: the ordering is applied to rows and columns alike. */
 int sf_lu_plan_logdet(sf_lu_plan *plan, sf_float *logabs, int *sign);
+/* Sigma of an LU plan where the caller wants it (see sf_chol_plan_selinv_values and DESIGN 8k; refusals as there, a Cholesky plan
+ * included).  outL[p] = Sigma(Li[p], j) for every position p of column j of L -- the diagonal positions, which the assembly skips,
+ * get Sigma_jj; outU[p] = Sigma(j, Ui[p]) for every position p of row j of U.  A plan whose U aliases L has one structure for both
+ * triangles: outU must be NULL (otherwise SF_ERR_ARG), and the upper triangle is what the _t form returns. */
+int sf_lu_plan_selinv_values(sf_lu_plan *plan, sf_float *outL /* nnz */, sf_float *outU /* unz; NULL when U aliases L */);
+int sf_lu_plan_selinv_values_device(sf_lu_plan *plan, sf_float *d_outL, sf_float *d_outU);
+/* the transposed entries at the same positions: outL[p] = Sigma(j, Li[p]), outU[p] = Sigma(Ui[p], j) */
+int sf_lu_plan_selinv_values_t(sf_lu_plan *plan, sf_float *outL, sf_float *outU);
+int sf_lu_plan_selinv_values_t_device(sf_lu_plan *plan, sf_float *d_outL, sf_float *d_outU);
+/* out[t] = tr(Sigma M(VL_t, VU_t)) = sum_ij Sigma(j, i) M_ij for the matrix sf_lu_plan_set_values(VL_t, VU_t) would assemble: an
+ * entry of L meets the U-side Sigma, an entry of U the L-side one, the diagonal counts once (from U, which stores it) -- for
+ * dA/dtheta the derivative of log|det A|.  VU / ldvu as VL / ldvl with unz; U aliasing L: VU must be NULL, VL feeds both
+ * triangles.  SF_SEL_MAPPED: VL is the caller's one array (nsrc doubles per column, both parts of the stored map read from it) and
+ * VU must be NULL.  Otherwise as sf_chol_plan_selinv_trace. */
+int sf_lu_plan_selinv_trace(sf_lu_plan *plan, sf_long m, const sf_float *VL, sf_long ldvl, const sf_float *VU /* or NULL */, sf_long ldvu,
+                            int flags /* 0 | SF_SEL_MAPPED */, sf_float *out /* m */);
+int sf_lu_plan_selinv_trace_device(sf_lu_plan *plan, sf_long m, const sf_float *dVL, sf_long ldvl, const sf_float *dVU, sf_long ldvu,
+                                   int flags, sf_float *d_out /* m */);
+/* out[k] = Sigma(rows[k], cols[k]) with (i, j) taken literally; outside the pattern of L + U: a quiet NaN, counted */
+int sf_lu_plan_selinv_entries(sf_lu_plan *plan, sf_long count, const sf_long *rows, const sf_long *cols, sf_float *out,
+                              sf_long *outside /* or NULL */);
 double sf_lu_plan_stat(const sf_lu_plan *plan, const char *name);
 int sf_lu_plan_set_profiling(sf_lu_plan *plan, int on);
 int sf_lu_plan_destroy(sf_lu_plan *plan);

@@ -293,6 +293,22 @@ lib.sf_lu_plan_selinv_diag.argtypes = [C.c_void_p, c_double_p]
 lib.sf_lu_plan_selinv_diag.restype = C.c_int
 lib.sf_lu_plan_logdet.argtypes = [C.c_void_p, c_double_p, C.POINTER(C.c_int)]
 lib.sf_lu_plan_logdet.restype = C.c_int
+# Sigma on the pattern, its traces and entries (sf_selinv_pattern.hip); device addresses travel as integers
+lib.sf_chol_plan_selinv_values.argtypes = [C.c_void_p, c_double_p]
+lib.sf_chol_plan_selinv_values_device.argtypes = [C.c_void_p, C.c_void_p]
+for _n in ("sf_lu_plan_selinv_values", "sf_lu_plan_selinv_values_t"):
+    getattr(lib, _n).argtypes = [C.c_void_p, c_double_p, c_double_p]
+    getattr(lib, _n + "_device").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+lib.sf_chol_plan_selinv_trace.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, C.c_int, c_double_p]
+lib.sf_chol_plan_selinv_trace_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+lib.sf_lu_plan_selinv_trace.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64, C.c_int, c_double_p]
+lib.sf_lu_plan_selinv_trace_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+for _n in ("sf_chol_plan_selinv_entries", "sf_lu_plan_selinv_entries"):
+    getattr(lib, _n).argtypes = [C.c_void_p, C.c_int64, c_long_p, c_long_p, c_double_p, c_long_p]
+for _n in ("sf_chol_plan_selinv_values", "sf_chol_plan_selinv_values_device", "sf_lu_plan_selinv_values", "sf_lu_plan_selinv_values_device",
+           "sf_lu_plan_selinv_values_t", "sf_lu_plan_selinv_values_t_device", "sf_chol_plan_selinv_trace", "sf_chol_plan_selinv_trace_device",
+           "sf_lu_plan_selinv_trace", "sf_lu_plan_selinv_trace_device", "sf_chol_plan_selinv_entries", "sf_lu_plan_selinv_entries"):
+    getattr(lib, _n).restype = C.c_int
 lib.sf_lu_plan_stat.argtypes = [C.c_void_p, C.c_char_p]
 lib.sf_lu_plan_stat.restype = C.c_double
 lib.sf_lu_plan_set_profiling.argtypes = [C.c_void_p, C.c_int]

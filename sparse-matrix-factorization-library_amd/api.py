@@ -635,7 +635,159 @@ class _DeviceIOMixin:
         check(fn(self._h, A.data_ptr() or None), fn.__name__)
 
 
-class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin, _DeviceIOMixin):
+SEL_MAX_M = 64      # SF_SEL_MAX_M
+
+
+def _value_block(V, rows, what):
+    """a host block of value arrays: 1-D (rows,) or 2-D (rows, m), any memory order -> (array, m, leading dimension, was 1-D).
+    A float64 block with unit stride along the rows (a column-major array or a row slice of one) is passed as it is."""
+    V = np.asarray(V)
+    if V.ndim not in (1, 2) or V.shape[0] != rows:
+        raise ValueError(f"{what}: expected shape ({rows},) or ({rows}, m), got {V.shape}")
+    one = V.ndim == 1
+    m = 1 if one else V.shape[1]
+    if m > SEL_MAX_M:
+        raise ValueError(f"{what}: at most {SEL_MAX_M} value arrays per call, got {m}")
+    ldmin = max(rows, 1)
+    if one:
+        return _f64(V), 1, ldmin, True
+    direct = V.dtype == np.float64 and (rows <= 1 or V.strides[0] == 8) and (m <= 1 or (V.strides[1] % 8 == 0 and V.strides[1] >= 8 * ldmin))
+    if not direct:
+        V = np.asfortranarray(V, dtype=np.float64)
+    ld = ldmin if m <= 1 else V.strides[1] // 8
+    return V, m, ld, False
+
+
+class _SelinvPatternMixin:
+    """Sigma = A^-1 read where the caller wants it, after selinv() (sf_*_plan_selinv_values / _trace / _entries).
+    Everything is in permuted space, like get_selinv."""
+
+    def _sel_fn(self, what):
+        return getattr(lib, ("sf_lu_plan_" if isinstance(self, LUPlan) else "sf_chol_plan_") + what)
+
+    def _own_u(self):
+        return isinstance(self, LUPlan) and not self._alias
+
+    def selinv_values(self, transposed=False):
+        """Sigma on the structure the plan was created with: CholPlan -> S with S[p] = Sigma(Li[p], j) for every position p of
+        column j; LUPlan -> (SL, SU) with SU[p] = Sigma(j, Ui[p]) for every position of row j of U, or SL alone when U aliases L.
+        transposed (LUPlan): Sigma(j, Li[p]) and Sigma(Ui[p], j) instead."""
+        lu = isinstance(self, LUPlan)
+        if transposed and not lu:
+            raise ValueError("selinv_values: Sigma of a Cholesky plan is symmetric, there is no transposed form")
+        SL = np.zeros(max(self._nnz, 1), dtype=np.float64)
+        if not lu:
+            check(lib.sf_chol_plan_selinv_values(self._h, _dp(SL)), "sf_chol_plan_selinv_values")
+            return SL[:self._nnz]
+        SU = np.zeros(max(self._unz, 1), dtype=np.float64) if self._own_u() else None
+        fn = lib.sf_lu_plan_selinv_values_t if transposed else lib.sf_lu_plan_selinv_values
+        check(fn(self._h, _dp(SL), _dp(SU) if SU is not None else None), fn.__name__)
+        return (SL[:self._nnz], SU[:self._unz]) if SU is not None else SL[:self._nnz]
+
+    def selinv_values_device(self, out, outU=None, transposed=False):
+        """selinv_values into device tensors (1-D float64, nnz / unz entries; outU: LUPlan with its own U structure)"""
+        lu = isinstance(self, LUPlan)
+        if transposed and not lu:
+            raise ValueError("selinv_values_device: Sigma of a Cholesky plan is symmetric, there is no transposed form")
+        if (outU is not None) != self._own_u():
+            raise ValueError("selinv_values_device: outU is for an LUPlan with its own U structure, and needed there")
+        L, _, _, one = _dev_tensor(out, self._nnz, self.device, "selinv_values_device", writable=True)
+        args = [L.data_ptr() or None]
+        if outU is not None:
+            U, _, _, oneu = _dev_tensor(outU, self._unz, self.device, "selinv_values_device (outU)", writable=True)
+            one = one and oneu
+            args.append(U.data_ptr() or None)
+        elif lu:
+            args.append(None)
+        if not one:
+            raise ValueError("selinv_values_device: the outputs must be 1-D")
+        self._dev_sync()
+        fn = self._sel_fn("selinv_values_t_device" if transposed else "selinv_values_device")
+        check(fn(self._h, *args), fn.__name__)
+        return (out, outU) if outU is not None else out
+
+    def _trace_rows(self, mapped, what):
+        if not mapped:
+            return self._nnz
+        if getattr(self, "_nsrc", None) is None:
+            raise ValueError(f"{what}: mapped=True needs a value map (set_value_map)")
+        return self._nsrc
+
+    def selinv_trace(self, V, VU=None, mapped=False):
+        """tr(Sigma M(V)) for the matrix set_values(V) would assemble: V 1-D (nnz,) -> float, 2-D (nnz, m) -> (m,), m <= 64, any
+        memory order.  LUPlan with its own U structure: VU likewise with unz rows.  mapped: V is in the caller's own layout
+        (nsrc rows) and read through the map of set_value_map (VU: None)."""
+        what = "selinv_trace"
+        need_u = self._own_u() and not mapped
+        if (VU is not None) != need_u:
+            raise ValueError(f"{what}: VU is for an LUPlan with its own U structure (unmapped), and needed there")
+        A, m, ld, one = _value_block(V, self._trace_rows(mapped, what), what)
+        args = [m, _dp(A), ld]
+        if isinstance(self, LUPlan):
+            if need_u:
+                B, mu, ldu, oneu = _value_block(VU, self._unz, what + " (VU)")
+                if (mu, oneu) != (m, one):
+                    raise ValueError(f"{what}: VU must have as many columns as V")
+                args += [_dp(B), ldu]
+            else:
+                args += [None, 0]
+        out = np.zeros(max(m, 1), dtype=np.float64)
+        if m:
+            fn = self._sel_fn("selinv_trace")
+            check(fn(self._h, *args, 1 if mapped else 0, _dp(out)), fn.__name__)
+        return float(out[0]) if one else out[:m]
+
+    def selinv_trace_device(self, V, VU=None, out=None, mapped=False):
+        """selinv_trace on device tensors ((rows,) or column-major (rows, m)); out: (m,) float64 on the device, allocated when None"""
+        what = "selinv_trace_device"
+        need_u = self._own_u() and not mapped
+        if (VU is not None) != need_u:
+            raise ValueError(f"{what}: VU is for an LUPlan with its own U structure (unmapped), and needed there")
+        A, m, ld, one = _dev_tensor(V, self._trace_rows(mapped, what), self.device, what)
+        if m > SEL_MAX_M:
+            raise ValueError(f"{what}: at most {SEL_MAX_M} value arrays per call, got {m}")
+        args = [m, A.data_ptr() or None, ld]
+        if isinstance(self, LUPlan):
+            if need_u:
+                B, mu, ldu, oneu = _dev_tensor(VU, self._unz, self.device, what + " (VU)")
+                if (mu, oneu) != (m, one):
+                    raise ValueError(f"{what}: VU must have as many columns as V")
+                args += [B.data_ptr() or None, ldu]
+            else:
+                args += [None, 0]
+        torch = None
+        if out is None:
+            torch = self._dev_sync()
+            out = torch.empty(m, dtype=torch.float64, device=f"cuda:{self.device}")
+        O, ko, _, oneo = _dev_tensor(out, m, self.device, what + " (out)", writable=True)
+        if not oneo:
+            raise ValueError(f"{what}: out must have shape ({m},), got {tuple(out.shape)}")
+        if m:
+            if torch is None:
+                self._dev_sync()
+            fn = self._sel_fn("selinv_trace_device")
+            check(fn(self._h, *args, 1 if mapped else 0, O.data_ptr()), fn.__name__)
+        return out
+
+    def selinv_entries(self, rows, cols):
+        """(values, outside): values[k] = Sigma(rows[k], cols[k]) for permuted indices (CholPlan: either triangle; LUPlan: (i, j)
+        literally); a pair outside the factor's pattern gets NaN and is counted in `outside`"""
+        rows, cols = _i64(rows), _i64(cols)
+        if rows.ndim != 1 or rows.shape != cols.shape:
+            raise ValueError(f"selinv_entries: rows and cols must be 1-D of one length, got {rows.shape} and {cols.shape}")
+        out = np.zeros(max(rows.size, 1), dtype=np.float64)
+        outside = C.c_int64(0)
+        fn = self._sel_fn("selinv_entries")
+        check(fn(self._h, rows.size, _lp(rows), _lp(cols), _dp(out), C.byref(outside)), fn.__name__)
+        return out[:rows.size], int(outside.value)
+
+    def logdet_grad(self, dA, dAU=None):
+        """selinv_trace(dA): for dA = dA/dtheta in set_values order the derivative of logdet() with respect to theta -- of
+        log det A for a CholPlan, of log|det A| for an LUPlan (dAU: the U part, LUPlan with its own U structure)"""
+        return self.selinv_trace(dA, dAU)
+
+
+class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin, _DeviceIOMixin, _SelinvPatternMixin):
     """Device-resident supernodal Cholesky (flat ABI).  Raises if no HIP device is present.
     phase/load_top: multi-GPU sharding (sf_chol_plan_create_sharded); default = the whole matrix on one device.
     rank/nranks (with phase): distributed top (sf_chol_plan_create_distributed), run with factorize_phase(0) and then
@@ -896,7 +1048,7 @@ class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, 
         self.close()
 
 
-class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin, _DeviceIOMixin):
+class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin, _DeviceIOMixin, _SelinvPatternMixin):
     """Device-resident supernodal no-pivot LU (flat ABI, sf_lu_plan_*).  `sym` comes from analyze(..., method='lu').
     phase/load_top/rank/nranks: distributed multi-GPU plan (sf_lu_plan_create_distributed), as CholPlan."""
 

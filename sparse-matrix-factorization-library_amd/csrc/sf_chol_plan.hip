@@ -53,7 +53,7 @@ int sf_chol_plan_destroy(sf_chol_plan* p) {
                     p->d_Up, p->d_Ui, p->d_Ux, p->d_Xp, p->d_pack, p->d_piv, p->d_resid, p->d_loadmask, p->d_loadmapL, p->d_loadmapU, p->d_solve, p->d_solve_sync, p->d_x, p->d_relmap, p->d_scratch, p->d_status, p->d_fill, p->d_solveT, p->d_solveT_list, p->d_xm,
                     p->d_sel, p->d_sel_diag, p->d_sel_units, p->d_sel_pairs, p->d_sel_scratch,
                     p->d_rf_ptr, p->d_rf_col, p->d_rf_pos, p->d_rf_cptr, p->d_rf_ccol, p->d_rf_cpos, p->d_rf_vec, p->d_cond, p->d_qf,
-                    p->d_perm, p->d_vmap, p->d_dio_part, p->d_gram};
+                    p->d_perm, p->d_vmap, p->d_dio_part, p->d_gram, p->d_sp_pos, p->d_sp_offd, p->d_sp_part, p->d_sp_stage};
     for (void* q : ptrs)
         if (q && !(q == (void*)p->d_Lsx && p->factor_borrowed)) (void)hipFree(q);      // (a borrowed factor buffer goes back to its lender)
     if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
@@ -1177,6 +1177,13 @@ double sf_chol_plan_stat(const sf_chol_plan* p, const char* name) {
     if (k == "last_selinv_ms") return p->last_selinv_ms;
     if (k == "flops_selinv") return p->flops_selinv;
     if (k == "selinv_valid") return (p->d_sel && p->sel_gen == p->factor_gen) ? 1.0 : 0.0;
+    if (k == "bytes_selinv_pattern") return (double)p->bytes_selinv_pattern;
+    if (k == "last_selinv_pattern_ms") return p->last_selinv_pattern_ms;
+    if (k == "last_selinv_outside") return (double)p->last_selinv_outside;
+    if (k == "selinv_pattern_chunk") return sf_selpat_constant(0);
+    if (k == "selinv_pattern_tile") return sf_selpat_constant(1);
+    if (k == "selinv_entries_chunk") return sf_selpat_constant(2);
+    if (k == "selinv_pattern_max_m") return sf_selpat_constant(3);
     if (k == "last_refine_iters") return (double)p->last_refine_iters;
     if (k == "last_refine_berr0") return p->last_refine_berr0;
     if (k == "last_refine_berr") return p->last_refine_berr;

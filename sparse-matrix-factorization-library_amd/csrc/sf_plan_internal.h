@@ -369,6 +369,17 @@ struct sf_chol_plan {
     double* d_sel_scratch = nullptr;
     size_t bytes_selinv = 0;
     double last_selinv_ms = 0, flops_selinv = 0;
+    // sf_*_plan_selinv_values / _trace / _entries (sf_selinv_pattern.hip): the position of every entry of the structure in one panel
+    // set (posL, then posU of an LU plan with its own U structure) with the off-diagonal marks of a Cholesky plan, the parts and
+    // results of a trace, the staging buffer of the (row, column) pairs -- each allocated by the first call that needs it
+    // (bytes_selinv_pattern, not in bytes_device)
+    int64_t* d_sp_pos = nullptr;
+    uint8_t* d_sp_offd = nullptr;
+    double* d_sp_part = nullptr;
+    void* d_sp_stage = nullptr;
+    size_t bytes_selinv_pattern = 0;
+    double last_selinv_pattern_ms = 0;
+    int64_t last_selinv_outside = 0;
     // sf_chol_plan_residual / sf_chol_plan_refine (sf_refine.hip): A by rows as positions into d_Lx / d_Ux (unsymmetric LU: also by
     // columns, for |A|_1), the vectors b | x | best x | r | w and the scalars; one set of allocations made by the first call
     // (not in bytes_device).  rf_anorm_gen = factor_gen the stored |A|_1 belongs to.
@@ -467,6 +478,8 @@ int sf_apply_chunks(sf_chol_plan* p, const SfApply& a, SfStretch& t, Body&& body
 // about to be enqueued with run_launches (which records and publishes the piece events while dl_active is set);
 // sf_dl_end publishes what is left, waits for the workers and returns SF_OK or the first error.
 int sf_dl_begin(sf_chol_plan* p, double* host_out);
+// the constants of sf_selinv_pattern.hip for sf_chol_plan_stat: 0 the column chunk, 1 entries per part, 2 pairs per staging trip, 3 max m
+double sf_selpat_constant(int which);
 // per-supernode fingerprints (k_factor_hash) of the factor the plan holds, in the reference layout's index space; 0 for panels this
 // rank does not store.  Computed once per factorization (about one read of the factor), then cached.
 extern "C" int sf_plan_panel_hashes(sf_chol_plan* p, const uint64_t** out);
