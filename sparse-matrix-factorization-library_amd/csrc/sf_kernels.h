@@ -308,6 +308,32 @@ void launch_lu_selinv_diag(int64_t n, const double* SL, const SelStruct& t, doub
 // buf: ceil(n / 256) partial sums, then sum log|U_jj| and the parity of the negative U_jj (as a double); neg: ceil(n / 256) counts
 void launch_lu_logdet(int64_t n, const double* PU, const SelStruct& t, double* buf, int32_t* neg, hipStream_t st);
 
+// ---- Sigma on the pattern of A (sf_selinv_pattern.hip, sf_*_plan_selinv_values / _trace / _entries) ----
+constexpr int SELPAT_CHUNK = 8;                         // columns of V a lane keeps partial sums for at a time (registers, no scratch)
+constexpr int SELPAT_EPT = 8;                           // entries per lane: that many independent map -> Sigma gathers in flight
+constexpr int SELPAT_TILE = 256 * SELPAT_EPT;           // entries per workgroup = per part
+constexpr int SELPAT_MAX_M = 64;                        // value arrays per call
+constexpr int64_t SELPAT_ENT_CHUNK = (int64_t)1 << 16;  // (row, column) pairs per trip through the staging buffer
+constexpr int SELPAT_GATHER_GRID = 256 * 16;            // workgroups of the gather at most: it strides above 256 times that many entries
+// one launch each, on the kernels of sf_selinv_pattern.hip; the plans' entry points run these and nothing else
+// pos[p] = the offset of entry p of the structure (Lp, Li) in one panel set (Xp: the panels' offsets), offd[p] = (row != column)
+// when offd is not null; n <= 0: nothing launched
+void launch_selpat_build(const int64_t* Lp, const int32_t* Li, int32_t n, const int32_t* Super, const int32_t* SuperMap, const int64_t* Lsip,
+                         const int32_t* Lsi, const int64_t* Xp, int64_t* pos, uint8_t* offd, hipStream_t st);
+// out[p] = S[pos[p]], p < count
+void launch_selpat_gather(const int64_t* pos, int64_t count, const double* S, double* out, hipStream_t st);
+// part[t * nparts + part0 + b] = sum over the entries p of tile b of w_p S[map[p] + shift] V_t[p], t < m, b < ceil(count / SELPAT_TILE);
+// map[p] < 0: the entry is skipped; offd: null or the marks of w_p = 2; mapped: V_t[p] = V[vmap[p] + t ldv] (vmap[p] < 0: 0), otherwise
+// V[p + t ldv].  Returns the number of workgroups (= parts per column) launched; count <= 0: 0, nothing launched
+int64_t launch_selpat_part(bool mapped, const int64_t* map, const uint8_t* offd, int64_t count, const double* S, int64_t shift, const double* V,
+                           int64_t ldv, const int64_t* vmap, int m, double* part, int64_t part0, int64_t nparts, hipStream_t st);
+// out[t] = the sum of part[t * nparts .. + nparts) in the fixed order of k_selpat_final, t < m
+void launch_selpat_final(const double* part, int64_t nparts, int m, double* out, hipStream_t st);
+// out[k] = Sigma(rows[k], cols[k]), k < count, a quiet NaN outside the pattern, counted in *outside (added to what it holds);
+// lu != 0: i >= j from S, i < j from S + xC
+void launch_selpat_entries(const int64_t* rows, const int64_t* cols, int64_t count, int lu, int64_t xC, const double* S, const SelStruct& t,
+                           double* out, unsigned long long* outside, hipStream_t st);
+
 void launch_noop(hipStream_t st);
 
 // ---- residual and iterative refinement (sf_refine.hip, sf_chol_plan_residual / sf_chol_plan_refine) ----

@@ -31,11 +31,7 @@
 
 namespace sf {
 
-constexpr int SELPAT_CHUNK = 8;                         // columns of V a lane keeps partial sums for at a time (registers, no scratch)
-constexpr int SELPAT_EPT = 8;                           // entries per lane: that many independent map -> Sigma gathers in flight
-constexpr int SELPAT_TILE = 256 * SELPAT_EPT;           // entries per workgroup = per part
-constexpr int SELPAT_MAX_M = 64;                        // value arrays per call
-constexpr int64_t SELPAT_ENT_CHUNK = (int64_t)1 << 16;  // (row, column) pairs per trip through the staging buffer
+// (the SELPAT_* constants: sf_kernels.h)
 
 // position of the first element >= key in the ascending array a[0..n)
 __device__ __forceinline__ int selpat_lower_bound(const int32_t* __restrict__ a, int n, int32_t key) {
@@ -182,6 +178,45 @@ k_selpat_entries(const int64_t* __restrict__ rows, const int64_t* __restrict__ c
     out[k] = S[off + ((lu && i < j) ? xC : 0)];
 }
 
+// ---- the launchers (sf_kernels.h): one launch each; the host side below and the per-launch tests run these and nothing else ----
+void launch_selpat_build(const int64_t* Lp, const int32_t* Li, int32_t n, const int32_t* Super, const int32_t* SuperMap, const int64_t* Lsip,
+                         const int32_t* Lsi, const int64_t* Xp, int64_t* pos, uint8_t* offd, hipStream_t st) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_selpat_build, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, st, Lp, Li, n, Super, SuperMap, Lsip, Lsi, Xp,
+                       pos, offd);
+}
+
+void launch_selpat_gather(const int64_t* pos, int64_t count, const double* S, double* out, hipStream_t st) {
+    if (count <= 0) return;
+    const int64_t blocks = std::min<int64_t>((count + 255) / 256, SELPAT_GATHER_GRID);
+    hipLaunchKernelGGL(k_selpat_gather, dim3((unsigned)blocks), dim3(256), 0, st, pos, count, S, out);
+}
+
+int64_t launch_selpat_part(bool mapped, const int64_t* map, const uint8_t* offd, int64_t count, const double* S, int64_t shift, const double* V,
+                           int64_t ldv, const int64_t* vmap, int m, double* part, int64_t part0, int64_t nparts, hipStream_t st) {
+    if (count <= 0) return 0;
+    const int64_t nt = (count + SELPAT_TILE - 1) / SELPAT_TILE;
+    if (mapped)
+        hipLaunchKernelGGL(k_selpat_part<true>, dim3((unsigned)nt), dim3(256), 0, st, map, offd, count, S, shift, V, ldv, vmap, m, part, part0,
+                           nparts);
+    else
+        hipLaunchKernelGGL(k_selpat_part<false>, dim3((unsigned)nt), dim3(256), 0, st, map, offd, count, S, shift, V, ldv, vmap, m, part, part0,
+                           nparts);
+    return nt;
+}
+
+void launch_selpat_final(const double* part, int64_t nparts, int m, double* out, hipStream_t st) {
+    if (m <= 0) return;
+    hipLaunchKernelGGL(k_selpat_final, dim3((unsigned)m), dim3(256), 0, st, part, nparts, out);
+}
+
+void launch_selpat_entries(const int64_t* rows, const int64_t* cols, int64_t count, int lu, int64_t xC, const double* S, const SelStruct& t,
+                           double* out, unsigned long long* outside, hipStream_t st) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_selpat_entries, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, rows, cols, count, lu, xC, S, t.Super, t.SuperMap,
+                       t.Lsip, t.Lsi, t.Xp, out, outside);
+}
+
 }  // namespace sf
 
 // ===========================================================================================================================
@@ -214,14 +249,9 @@ int selpat_positions(sf_chol_plan* p) {
             return rc;
         }
     const int64_t* xp = p->lu ? p->d_Xp : p->d_Lsxp;
-    if (p->n > 0) {
-        const dim3 g((unsigned)((p->n + 255) / 256));
-        hipLaunchKernelGGL(sf::k_selpat_build, g, dim3(256), 0, p->stream, p->d_Lp, p->d_Li, (int32_t)p->n, p->d_Super, p->d_SuperMap,
-                           p->d_Lsip, p->d_Lsi, xp, pos, offd);
-        if (own_u)
-            hipLaunchKernelGGL(sf::k_selpat_build, g, dim3(256), 0, p->stream, p->d_Up, p->d_Ui, (int32_t)p->n, p->d_Super, p->d_SuperMap,
-                               p->d_Lsip, p->d_Lsi, xp, pos + nl, (uint8_t*)nullptr);
-    }
+    sf::launch_selpat_build(p->d_Lp, p->d_Li, (int32_t)p->n, p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, xp, pos, offd, p->stream);
+    if (own_u)
+        sf::launch_selpat_build(p->d_Up, p->d_Ui, (int32_t)p->n, p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, xp, pos + nl, nullptr, p->stream);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(p->stream) != hipSuccess) {
         (void)hipFree(pos);
         if (offd) (void)hipFree(offd);
@@ -253,9 +283,7 @@ int selpat_stage(sf_chol_plan* p) {
 }
 
 void gather(sf_chol_plan* p, const int64_t* pos, int64_t count, const double* S, double* out) {
-    if (count <= 0) return;
-    const int64_t blocks = std::min<int64_t>((count + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(sf::k_selpat_gather, dim3((unsigned)blocks), dim3(256), 0, p->stream, pos, count, S, out);
+    sf::launch_selpat_gather(pos, count, S, out, p->stream);
 }
 
 // Sigma on the structure into device memory: dL (nnz), dU (unz; LU plans with their own U structure).  transposed: Sigma(j, i) where
@@ -312,17 +340,10 @@ void trace_launch(sf_chol_plan* p, const TraceSide* side, int nside, bool mapped
     int64_t part0 = 0;
     for (int k = 0; k < nside; ++k) {
         const TraceSide& s = side[k];
-        const int64_t nt = tiles(s.count);
-        if (nt <= 0) continue;
-        if (mapped)
-            hipLaunchKernelGGL(sf::k_selpat_part<true>, dim3((unsigned)nt), dim3(256), 0, p->stream, s.map, s.offd, s.count, (const double*)p->d_sel,
-                               s.shift, s.V, s.ldv, s.vmap, m, p->d_sp_part, part0, nparts);
-        else
-            hipLaunchKernelGGL(sf::k_selpat_part<false>, dim3((unsigned)nt), dim3(256), 0, p->stream, s.map, s.offd, s.count, (const double*)p->d_sel,
-                               s.shift, s.V, s.ldv, s.vmap, m, p->d_sp_part, part0, nparts);
-        part0 += nt;
+        part0 += sf::launch_selpat_part(mapped, s.map, s.offd, s.count, p->d_sel, s.shift, s.V, s.ldv, s.vmap, m, p->d_sp_part, part0, nparts,
+                                        p->stream);
     }
-    hipLaunchKernelGGL(sf::k_selpat_final, dim3((unsigned)m), dim3(256), 0, p->stream, (const double*)p->d_sp_part, nparts, d_res);
+    sf::launch_selpat_final(p->d_sp_part, nparts, m, d_res, p->stream);
 }
 
 // VL / VU: device memory.  d_out: device memory of the caller's, or null -- the results then go to `out` on the host.
@@ -417,6 +438,7 @@ int entries_entry(sf_chol_plan* p, bool lu, sf_long count, const sf_long* rows, 
     double* d_val = (double*)(d_cols + CH);
     unsigned long long* d_cnt = (unsigned long long*)(d_val + CH);
     hipStream_t st = p->stream;
+    const sf::SelStruct tab{p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, lu ? p->d_Xp : p->d_Lsxp, nullptr, nullptr};
     HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), st));
     SfStretch t{p};
     for (int64_t k0 = 0; k0 < count; k0 += CH) {
@@ -424,9 +446,7 @@ int entries_entry(sf_chol_plan* p, bool lu, sf_long count, const sf_long* rows, 
         HIP_TRY(hipMemcpyAsync(d_rows, rows + k0, (size_t)c * sizeof(int64_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_cols, cols + k0, (size_t)c * sizeof(int64_t), hipMemcpyHostToDevice, st));
         if (int rc = t.open()) return rc;
-        hipLaunchKernelGGL(sf::k_selpat_entries, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, st, (const int64_t*)d_rows, (const int64_t*)d_cols,
-                           c, lu ? 1 : 0, p->xC, (const double*)p->d_sel, p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi,
-                           lu ? p->d_Xp : p->d_Lsxp, d_val, d_cnt);
+        sf::launch_selpat_entries(d_rows, d_cols, c, lu ? 1 : 0, p->xC, p->d_sel, tab, d_val, d_cnt, st);
         if (int rc = t.mark()) return rc;
         HIP_TRY(hipMemcpyAsync(out + k0, d_val, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, st));
         if (int rc = t.close(false)) return rc;     // (the pageable copies above are done before the next chunk overwrites the stage)

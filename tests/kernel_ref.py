@@ -936,3 +936,162 @@ def loadmap_drop_emulate(drop, map_, fault=None):
     nb, passes = strided_visit(len(drop), 256, fault)
     map_[drop[:nb * 256 * passes]] = -1
     return map_
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Sigma on the pattern of A, one launch at a time (csrc/sf_selinv_pattern.hip): tests/test_kernels_selpat.py
+# ---------------------------------------------------------------------------------------------------------------------
+SELPAT_TILE, SELPAT_EPT, SELPAT_CHUNK, SELPAT_GATHER_GRID = 2048, 8, 8, 4096     # sf_kernels.h
+# depth of one part: the lane's 8 fused multiply-adds, 6 shuffle levels, 2 additions of the four waves' sums (the weight 2 is exact)
+SELPAT_PART_DEPTH = SELPAT_EPT + 6 + 2
+# every single fault the emulations below can inject; tests/test_kernels_selpat.py shows for each that a checker rejects it
+SELPAT_FAULTS = ("weight everywhere", "dead entry read", "tail lane dropped", "part0 ignored", "stride is own tiles", "column past m",
+                 "shift ignored", "vmap ignored", "first 256 parts", "32-bit product", "diagonal row searched", "offd inverted", "no end guard",
+                 "triangle swapped", "counter reset", "gather no stride")
+
+
+def selpat_tiles(count):
+    return -(-max(int(count), 0) // SELPAT_TILE)
+
+
+def selpat_final_depth(nparts):
+    """the longest chain of additions behind one result of k_selpat_final: ceil(nparts / 256) serial steps, 8 tree levels"""
+    return -(-int(nparts) // 256) + 8
+
+
+def _wrap32(v):
+    v = int(v) & 0xFFFFFFFF
+    return v - (1 << 32) if v >= 1 << 31 else v
+
+
+def selpat_build_emulate(tb, Lp, Li, pos, offd, fault=None):
+    """k_selpat_build on the structure tb (SelTables): pos[p] = Xp[s] + (j - c0) nsrow + (the row's position in the supernode's row
+    list) for every entry p of column j, offd[p] = (row != j) when offd is given.  Columns without entries are skipped, as a lane
+    with an empty loop is.  Faults: "32-bit product" -- (j - c0) nsrow wraps as a signed 32-bit product; "diagonal row searched" -- the
+    nscol offset is missing for a row below the diagonal block; "offd inverted" -- the diagonal is marked instead."""
+    for j in np.flatnonzero(np.diff(Lp)):
+        j = int(j)
+        s = int(tb.SuperMap[j])
+        c0, c1 = int(tb.Super[s]), int(tb.Super[s + 1])
+        nsrow, nscol = tb.nsrow(s), c1 - c0
+        prod = (j - c0) * nsrow
+        col = int(tb.Xp[s]) + (_wrap32(prod) if fault == "32-bit product" else prod)
+        below = tb.rows(s)[nscol:]
+        for p in range(int(Lp[j]), int(Lp[j + 1])):
+            i = int(Li[p])
+            if i < c1:
+                si = i - c0
+            else:
+                si = (0 if fault == "diagonal row searched" else nscol) + int(np.searchsorted(below, i))
+            pos[p] = col + si
+            if offd is not None:
+                offd[p] = (i == j) if fault == "offd inverted" else (i != j)
+    return pos, offd
+
+
+def selpat_gather_emulate(pos, count, S, out, fault=None):
+    """k_selpat_gather: out[p] = S[pos[p]], p < count.  "gather no stride": the 4096 workgroups make one pass only"""
+    lim = min(count, SELPAT_GATHER_GRID * 256) if fault == "gather no stride" else count
+    out[:lim] = S[pos[:lim]]
+    return out
+
+
+def selpat_part_emulate(buf, mapped, map_, offd, vmap, count, s_off, shift, v_off, ldv, m, part_off, part0, nparts, fault=None):
+    """k_selpat_part on the image buf, in float64 and in the documented order: lane tid of tile b sums its entries b 2048 + tid + 256 e
+    in order of e (s v + acc rounded twice here, fused in the kernel -- the checkers bound the sum, they do not ask for its bits), a
+    6-level halving tree over the wave's 64 lanes, then (w0 + w1) + (w2 + w3).  Returns the number of tiles.  Faults: see SELPAT_FAULTS
+    and the table of tests/test_kernels_selpat.py."""
+    if count <= 0:
+        return 0
+    nt = selpat_tiles(count)
+    n_used = count // 256 * 256 if fault == "tail lane dropped" else count
+    pad = nt * SELPAT_TILE
+    p = np.arange(pad)
+    q = np.full(pad, -1, dtype=np.int64)
+    q[:n_used] = map_[:n_used]
+    live = q >= 0
+    if fault == "dead entry read":
+        live = p < n_used
+    sh = 0 if fault == "shift ignored" else shift
+    s = np.where(live, buf[np.where(live, s_off + q + sh, 0)], 0.0)
+    if offd is not None:
+        w = np.zeros(pad, dtype=bool)
+        w[:count] = np.asarray(offd[:count]) != 0
+        s = np.where(live & (w | (fault == "weight everywhere")), 2.0 * s, s)
+    if mapped and fault != "vmap ignored":
+        vq = np.full(pad, -1, dtype=np.int64)
+        vq[:count] = vmap[:count]
+        vq = np.where(live, vq, -1)
+    else:
+        vq = np.where(live, p, -1)
+    has_v = vq >= 0
+    shape = (nt, SELPAT_EPT, 256)
+    s, vq, has_v = s.reshape(shape), vq.reshape(shape), has_v.reshape(shape)
+    stride = nt if fault == "stride is own tiles" else nparts
+    first = 0 if fault == "part0 ignored" else part0
+    ncol = -(-m // SELPAT_CHUNK) * SELPAT_CHUNK if fault == "column past m" else m
+    for t in range(ncol):
+        acc = np.zeros((nt, 256))
+        if t < m:
+            for e in range(SELPAT_EPT):
+                v = buf[np.where(has_v[:, e], v_off + vq[:, e] + t * ldv, 0)]
+                acc = np.where(has_v[:, e], s[:, e] * v + acc, acc)
+        wv = acc.reshape(nt, 4, 64)
+        h = 32
+        while h:
+            wv = wv[..., :h] + wv[..., h:2 * h]
+            h //= 2
+        wv = wv[..., 0]
+        buf[part_off + t * stride + first + np.arange(nt)] = (wv[:, 0] + wv[:, 1]) + (wv[:, 2] + wv[:, 3])
+    return nt
+
+
+def selpat_final_emulate(buf, part_off, nparts, m, out_off, fault=None):
+    """k_selpat_final: per column lane k sums the parts k, k + 256, ... in order, then a halving tree over the 256 lanes.
+    "first 256 parts": one trip only"""
+    trips = 1 if fault == "first 256 parts" else -(-nparts // 256)
+    for t in range(m):
+        col = np.zeros(trips * 256)
+        lim = min(nparts, trips * 256)
+        col[:lim] = buf[part_off + t * nparts:part_off + t * nparts + lim]
+        v = np.zeros(256)
+        for row in col.reshape(trips, 256):
+            v = v + row
+        h = 128
+        while h:
+            v = v[:h] + v[h:2 * h]
+            h //= 2
+        buf[out_off + t] = v[0]
+    return buf
+
+
+def selpat_entries_emulate(tb, rows, cols, count, lu, xC, buf, s_off, out_off, outside, fault=None):
+    """k_selpat_entries: out[k] = Sigma(rows[k], cols[k]) by the search of the walk, NaN outside the pattern; returns the counter.
+    Faults: "no end guard" -- the search's result is compared without b < nb (what lies behind the supernode's rows in Lsi is read;
+    behind the end of Lsi: not found); "diagonal row searched"; "triangle swapped" -- LU i < j is read from the first arena;
+    "counter reset" -- the counter is overwritten with this launch's count"""
+    nout = 0
+    for k in range(count):
+        i, j = int(rows[k]), int(cols[k])
+        col, row = min(i, j), max(i, j)
+        s = int(tb.SuperMap[col])
+        c0, c1 = int(tb.Super[s]), int(tb.Super[s + 1])
+        nsrow, nscol = tb.nsrow(s), c1 - c0
+        nb = nsrow - nscol
+        si, found = row - c0, True
+        if row >= c1:
+            start = int(tb.Lsip[s]) + nscol
+            b = int(np.searchsorted(tb.Lsi[start:start + nb], row))
+            if fault == "no end guard":
+                found = start + b < len(tb.Lsi) and int(tb.Lsi[start + b]) == row
+            else:
+                found = b < nb and int(tb.Lsi[start + b]) == row
+            si = (0 if fault == "diagonal row searched" else nscol) + b
+        if not found:
+            buf[out_off + k] = np.nan
+            nout += 1
+            continue
+        off = int(tb.Xp[s]) + (col - c0) * nsrow + si
+        second = lu and i < j and fault != "triangle swapped"
+        buf[out_off + k] = buf[s_off + off + (xC if second else 0)]
+    return nout if fault == "counter reset" else outside + nout

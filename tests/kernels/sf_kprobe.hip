@@ -772,4 +772,79 @@ int kp_dev_absmax(double* buf, int64_t nbuf, int64_t v_off, int64_t count, int64
     return (int)d.rc;
 }
 
+// ---- Sigma on the pattern of A (csrc/sf_selinv_pattern.hip): tests/test_kernels_selpat.py ----
+// No double arena: the launch computes offsets and dereferences none.  pos: npos words, offd: npos bytes or null, both in and out
+int kp_selpat_build(const int64_t* Lp, const int32_t* Li, int32_t n, const int32_t* Super, const int32_t* SuperMap, int32_t nsuper,
+                    const int64_t* Lsip, const int32_t* Lsi, const int64_t* Xp, int64_t* pos, uint8_t* offd, int64_t npos) {
+    Dev d;
+    const int64_t* dLp = d.in(Lp, (int64_t)n + 1);
+    const int32_t* dLi = d.in(Li, Lp[n]);
+    const int32_t* dS = d.in(Super, (int64_t)nsuper + 1);
+    const int32_t* dSM = d.in(SuperMap, n);
+    const int64_t* dLsip = d.in(Lsip, (int64_t)nsuper + 1);
+    const int32_t* dLsi = d.in(Lsi, Lsip[nsuper]);
+    const int64_t* dXp = d.in(Xp, (int64_t)nsuper + 1);
+    int64_t* dpos = d.in(pos, npos);
+    uint8_t* doffd = offd ? d.in(offd, npos) : nullptr;
+    if (d.rc == hipSuccess) sf::launch_selpat_build(dLp, dLi, n, dS, dSM, dLsip, dLsi, dXp, dpos, doffd, 0);
+    d.finish();
+    d.out(pos, dpos, npos);
+    if (offd) d.out(offd, doffd, npos);
+    return (int)d.rc;
+}
+
+// pos: count entries
+int kp_selpat_gather(double* buf, int64_t nbuf, int64_t s_off, const int64_t* pos, int64_t count, int64_t out_off) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    const int64_t* dpos = d.in(pos, count);
+    if (d.rc == hipSuccess) sf::launch_selpat_gather(dpos, count, W + s_off, W + out_off, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+// map, offd (or null), vmap (or null): nmap entries each (nmap >= count: what lies past count is the test's); *launched = the
+// launcher's return value
+int kp_selpat_part(int mapped, const int64_t* map, const uint8_t* offd, const int64_t* vmap, int64_t nmap, int64_t count, double* buf,
+                   int64_t nbuf, int64_t s_off, int64_t shift, int64_t v_off, int64_t ldv, int m, int64_t part_off, int64_t part0,
+                   int64_t nparts, int64_t* launched) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    const int64_t* dmap = d.in(map, nmap);
+    const uint8_t* doffd = offd ? d.in(offd, nmap) : nullptr;
+    const int64_t* dvmap = vmap ? d.in(vmap, nmap) : nullptr;
+    if (d.rc == hipSuccess)
+        *launched = sf::launch_selpat_part(mapped != 0, dmap, doffd, count, W + s_off, shift, W + v_off, ldv, dvmap, m, W + part_off, part0,
+                                           nparts, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+int kp_selpat_final(double* buf, int64_t nbuf, int64_t part_off, int64_t nparts, int m, int64_t out_off) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    if (d.rc == hipSuccess) sf::launch_selpat_final(W + part_off, nparts, m, W + out_off, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    return (int)d.rc;
+}
+
+// rows, cols: count entries; the arena(s) at buf + s_off (lu: the second one xC doubles behind); *outside in and out
+int kp_selpat_entries(const int64_t* rows, const int64_t* cols, int64_t count, int lu, int64_t xC, double* buf, int64_t nbuf, int64_t s_off,
+                      const KpSel* sel, int64_t out_off, unsigned long long* outside) {
+    Dev d;
+    double* W = d.in(buf, nbuf);
+    const int64_t* R = d.in(rows, count);
+    const int64_t* Cc = d.in(cols, count);
+    const sf::SelStruct t = sel_in(d, sel);
+    unsigned long long* O = d.in(outside, 1);
+    if (d.rc == hipSuccess) sf::launch_selpat_entries(R, Cc, count, lu, xC, W + s_off, t, W + out_off, O, 0);
+    d.finish();
+    d.out(buf, W, nbuf);
+    d.out(outside, O, 1);
+    return (int)d.rc;
+}
+
 }  // extern "C"

@@ -61,7 +61,8 @@ def test_probe_compiles(tmp_path):
                  "kp_selinv_trinv", "kp_selinv_gemm", "kp_selinv_sum", "kp_selinv_finish", "kp_selinv_diag", "kp_logdet", "kp_lu_selinv_pack",
                  "kp_residual", "kp_loadmap_drop", "kp_refine_resid", "kp_refine_norms", "kp_refine_update", "kp_gram_slabs", "kp_gram_row",
                  "kp_gram2_col", "kp_dot", "kp_quadform", "kp_sample_fill", "kp_dev_load1", "kp_dev_store1", "kp_dev_pack", "kp_dev_unpack",
-                 "kp_dev_gather_values", "kp_dev_absmax"):
+                 "kp_dev_gather_values", "kp_dev_absmax", "kp_selpat_build", "kp_selpat_gather", "kp_selpat_part", "kp_selpat_final",
+                 "kp_selpat_entries"):
         assert f" T {name}" in nm
 
 
