@@ -134,6 +134,9 @@ lib.sf_handlers_fingerprint_fallbacks.argtypes = []
 lib.sf_handlers_fingerprint_fallbacks.restype = C.c_int64
 lib.sf_handlers_plan_builds.argtypes = [C.c_void_p, C.c_int]
 lib.sf_handlers_plan_builds.restype = C.c_int64
+# live blocks the plans of this process hold through the allocator seam (sf_device_mem.h): 0 device, 1 pinned host
+lib.sf_debug_live_blocks.argtypes = [C.c_int]
+lib.sf_debug_live_blocks.restype = C.c_long
 lib.sf_chol_plan_validate.argtypes = [C.c_void_p, c_double_p, c_double_p]
 lib.sf_chol_plan_validate.restype = C.c_int
 for _n in ("sf_chol_plan_residual", "sf_lu_plan_residual"):

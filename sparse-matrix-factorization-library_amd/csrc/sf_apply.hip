@@ -45,26 +45,39 @@ bool sf_blocks_overlap(const void* a, size_t na, const void* b, size_t nb) {
     return a0 < b0 + nb * sizeof(double) && b0 < a0 + na * sizeof(double);
 }
 
-int sf_device_alloc(void** ptr, size_t bytes) {
-    if (hipMalloc(ptr, bytes) != hipSuccess) {
+// ---- the seam of sf_device_mem.h: the only calls of the runtime's allocator outside the struct path's pool ----
+static std::atomic<long> g_live_blocks[2];      // 0 device, 1 pinned host
+
+static int seam_took(hipError_t e, void** ptr, int which) {
+    if (e != hipSuccess) {
         (void)hipGetLastError();
         *ptr = nullptr;
-        return SF_ERR_ALLOC;
+        return 1;
     }
-    return SF_OK;
+    if (*ptr) ++g_live_blocks[which];       // (an empty block is null and is never given back)
+    return 0;
 }
+int sf_dev_malloc(void** ptr, size_t bytes) { return seam_took(hipMalloc(ptr, bytes), ptr, 0); }
+int sf_host_malloc(void** ptr, size_t bytes) { return seam_took(hipHostMalloc(ptr, bytes, hipHostMallocDefault), ptr, 1); }
+void sf_dev_free(void* ptr) {
+    (void)hipFree(ptr);
+    --g_live_blocks[0];
+}
+void sf_host_free(void* ptr) {
+    (void)hipHostFree(ptr);
+    --g_live_blocks[1];
+}
+extern "C" long sf_debug_live_blocks(int which) { return (which == 0 || which == 1) ? g_live_blocks[which].load() : -1; }
 
 int sf_solve_many_block(sf_chol_plan* p) {
     if (p->d_xm) return SF_OK;
-    const size_t bytes = 2 * (size_t)p->n * sf::SVM_W * sizeof(double);
-    if (int rc = sf_device_alloc((void**)&p->d_xm, bytes)) return rc;
-    p->bytes_solve_many = bytes;
+    const size_t count = 2 * (size_t)p->n * sf::SVM_W;
+    if (int rc = p->d_xm.alloc(count)) return rc;
+    p->bytes_solve_many = count * sizeof(double);
     return SF_OK;
 }
 
-int sf_quadform_scratch(sf_chol_plan* p) {
-    return p->d_qf ? SF_OK : sf_device_alloc((void**)&p->d_qf, (size_t)(sf::QF_MAXB + 1) * sf::SVM_W * sizeof(double));
-}
+int sf_quadform_scratch(sf_chol_plan* p) { return p->d_qf ? SF_OK : p->d_qf.alloc((size_t)(sf::QF_MAXB + 1) * sf::SVM_W); }
 
 // The row-major copies of the top steps' diagonal blocks (d_solveT) are made from the U^T panels (Cholesky: the L panels) by BWD
 // and SOLVE and from the L panels by BWD_LT and TRANS, and neither may see the other's: a caller that alternates the two asks

@@ -1,6 +1,9 @@
-// Device plan of the supernodal Cholesky / LU numeric factorization: destruction, execution (run_launches), inspection, the
-// overlapped download, the solves and the statistics of a plan.  The plan itself -- the level-by-level sweep, its launch list and
-// task tables, the solve and download schedules, the device resources -- is built in sf_plan_build.hip.
+// Device plan of the supernodal Cholesky / LU numeric factorization: its release, the values and the stream it works on, execution
+// (run_launches, the segments of a distributed top, the hipGraph form), validation, the overlapped download, reading the factor
+// back and importing one, the pivoting policy and the statistics of a plan.  The plan itself -- the level-by-level sweep, its
+// launch list and task tables, the solve and download schedules, the device resources -- is built in sf_plan_build.hip; the
+// solves and everything else that takes columns through the resident factor live in files of their own (sf_solve.hip,
+// sf_apply.hip and the entry points' files).
 #include <sparseframe_hip.h>
 
 #include <algorithm>
@@ -45,38 +48,6 @@ size_t sf_reference_slot_size(int ndev, size_t min_mem) {
 int sf_plan_factor_borrowed(const sf_chol_plan* p) { return p && p->factor_borrowed ? 1 : 0; }
 
 int sf_chol_plan_destroy(sf_chol_plan* p) {
-    if (!p) return SF_OK;
-    if (p->dry) { delete p; return SF_OK; }
-    (void)hipSetDevice(p->device);
-    void* ptrs[] = {p->d_Lp, p->d_Li, p->d_Lx, p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, p->d_Lsxp,
-                    p->d_Lsx, p->d_info, p->d_potrf, p->d_trsm, p->d_steps, p->d_flags, p->d_tinv, p->d_probs, p->d_gtasks, p->d_stasks, p->d_ktprefix,
-                    p->d_Up, p->d_Ui, p->d_Ux, p->d_Xp, p->d_pack, p->d_piv, p->d_resid, p->d_loadmask, p->d_loadmapL, p->d_loadmapU, p->d_solve, p->d_solve_sync, p->d_x, p->d_relmap, p->d_scratch, p->d_status, p->d_fill, p->d_solveT, p->d_solveT_list, p->d_xm,
-                    p->d_sel, p->d_sel_diag, p->d_sel_units, p->d_sel_pairs, p->d_sel_scratch,
-                    p->d_rf_ptr, p->d_rf_col, p->d_rf_pos, p->d_rf_cptr, p->d_rf_ccol, p->d_rf_cpos, p->d_rf_vec, p->d_cond, p->d_qf,
-                    p->d_perm, p->d_vmap, p->d_dio_part, p->d_gram, p->d_sp_pos, p->d_sp_offd, p->d_sp_part, p->d_sp_stage};
-    for (void* q : ptrs)
-        if (q && !(q == (void*)p->d_Lsx && p->factor_borrowed)) (void)hipFree(q);      // (a borrowed factor buffer goes back to its lender)
-    if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
-    if (p->ev0) (void)hipEventDestroy(p->ev0);
-    if (p->ev1) (void)hipEventDestroy(p->ev1);
-    if (p->ev_s0) (void)hipEventDestroy(p->ev_s0);
-    if (p->ev_s1) (void)hipEventDestroy(p->ev_s1);
-    for (int k = 0; k < 2; ++k) {
-        if (p->ev_contrib[k]) (void)hipEventDestroy(p->ev_contrib[k]);
-        if (p->ev_reduced[k]) (void)hipEventDestroy(p->ev_reduced[k]);
-        if (p->ev_unpacked[k]) (void)hipEventDestroy(p->ev_unpacked[k]);
-    }
-    if (p->stream2) (void)hipStreamDestroy(p->stream2);
-    for (hipEvent_t e : p->dl_events)
-        if (e) (void)hipEventDestroy(e);
-    for (int w = 0; w < DL_WORKERS_MAX; ++w) {
-        if (p->dl_streams[w]) (void)hipStreamDestroy(p->dl_streams[w]);
-        for (int k = 0; k < 2; ++k)
-            if (p->dl_done[w][k]) (void)hipEventDestroy(p->dl_done[w][k]);
-    }
-    if (p->h_ring) (void)hipHostFree(p->h_ring);
-    if (p->d_ring) (void)hipFree(p->d_ring);
-    if (p->stream && p->own_stream) (void)hipStreamDestroy(p->stream);
     delete p;
     return SF_OK;
 }
@@ -595,8 +566,7 @@ int sf_chol_plan_set_stream(sf_chol_plan* p, void* stream) {
     if (p->dry) return SF_ERR_ARG;        // a schedule-only plan has no device side
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipStreamSynchronize(p->stream));
-    if (p->stream && p->own_stream) HIP_TRY(hipStreamDestroy(p->stream));
-    p->stream = (hipStream_t)stream;
+    p->stream.reset((hipStream_t)stream, false);
     p->own_stream = false;
     return SF_OK;
 }
@@ -610,8 +580,7 @@ static int factorize_graph(sf_chol_plan* p, int sync) {
     HIP_TRY(hipSetDevice(p->device));
     const double eps = p->lu ? p->piv_perturb * p->amax : 0.0, tol = p->lu ? p->piv_tol : 0.0;
     if (p->graph_exec && (p->graph_tol != tol || p->graph_eps != eps || p->graph_stream != p->stream)) {
-        (void)hipGraphExecDestroy(p->graph_exec);
-        p->graph_exec = nullptr;
+        p->graph_exec.reset();
     }
     bool fresh = false;
     if (!p->graph_exec) {
@@ -623,9 +592,11 @@ static int factorize_graph(sf_chol_plan* p, int sync) {
         p->capturing = false;
         const hipError_t e = hipStreamEndCapture(p->stream, &g);
         if (rc || e != hipSuccess || !g) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); return rc ? rc : SF_ERR_HIP; }
-        const hipError_t ei = hipGraphInstantiate(&p->graph_exec, g, nullptr, nullptr, 0);
+        hipGraphExec_t ge = nullptr;
+        const hipError_t ei = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
-        if (ei != hipSuccess) { p->graph_exec = nullptr; (void)hipGetLastError(); return SF_ERR_HIP; }
+        if (ei != hipSuccess) { (void)hipGetLastError(); return SF_ERR_HIP; }
+        p->graph_exec.reset(ge);
         p->graph_tol = tol; p->graph_eps = eps; p->graph_stream = p->stream;
     }
     // (the captured kernels compare the flags with graph_epoch and the graph clears the flags itself; p->epoch stays what it is for
@@ -663,7 +634,7 @@ int sf_chol_plan_validate(sf_chol_plan* p, sf_float* residual, sf_float* x_host)
     if (p->dry) return SF_ERR_ARG;        // a schedule-only plan has no device side
     HIP_TRY(hipSetDevice(p->device));
     if (!p->d_resid) {
-        HIP_TRY(hipMalloc((void**)&p->d_resid, (3 * (size_t)p->n + 4) * sizeof(double)));
+        if (p->d_resid.alloc(3 * (size_t)p->n + 4)) return SF_ERR_HIP;
         p->bytes_device += (3 * (size_t)p->n + 4) * sizeof(double);
     }
     std::vector<double> b(p->n), x(p->n);
@@ -918,14 +889,14 @@ int sf_dl_begin(sf_chol_plan* p, double* host_out) {
     if (p->dl_cpus_known == 0) dl_lookup_cpus(p);
     if (!p->h_ring) {
         const size_t rb = (size_t)std::max(p->dl_workers, p->dl_workers_fresh) * 2 * p->dl_slot * sizeof(double);
-        HIP_TRY(hipHostMalloc((void**)&p->h_ring, rb, hipHostMallocDefault));
+        if (p->h_ring.alloc(rb / sizeof(double))) return SF_ERR_HIP;
         if (p->lu && !p->dl_lu_direct) {
-            HIP_TRY(hipMalloc((void**)&p->d_ring, rb));
+            if (p->d_ring.alloc(rb / sizeof(double))) return SF_ERR_HIP;
             p->bytes_device += rb;
         }
         for (int w = 0; w < std::max(p->dl_workers, p->dl_workers_fresh); ++w) {
-            HIP_TRY(hipStreamCreateWithFlags(&p->dl_streams[w], hipStreamNonBlocking));
-            for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreateWithFlags(&p->dl_done[w][k], hipEventDisableTiming));
+            HIP_TRY(hipStreamCreateWithFlags(p->dl_streams[w].put(), hipStreamNonBlocking));
+            for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreateWithFlags(p->dl_done[w][k].put(), hipEventDisableTiming));
         }
     }
     // transparent huge pages for the destination (this box: THP = madvise): 512x fewer first-touch faults when the
@@ -1058,7 +1029,7 @@ int sf_chol_plan_get_factor(sf_chol_plan* p, sf_float* Lsx) {
     }
     // (sharded LU: panels not stored on this rank come back as zeros, k_pack_lu skips them)
     if (!p->d_pack) {
-        HIP_TRY(hipMalloc((void**)&p->d_pack, p->xsize * sizeof(double)));
+        if (p->d_pack.alloc(p->xsize)) return SF_ERR_HIP;
         p->bytes_device += p->xsize * sizeof(double);
     }
     sf::launch_pack_lu(p->d_Super, p->d_Lsip, p->d_Xp, p->d_Lsxp, (int32_t)p->nsuper, p->d_Lsx, p->d_Lsx + p->xC,
@@ -1081,14 +1052,13 @@ int sf_chol_plan_get_factor_range(sf_chol_plan* p, sf_long e_begin, sf_long e_en
         HIP_TRY(hipStreamSynchronize(p->stream));
         return SF_OK;
     }
-    double* tmp = nullptr;
-    HIP_TRY(hipMalloc((void**)&tmp, (e_end - e_begin) * sizeof(double)));
+    sf::DevMem<double> tmp;
+    if (tmp.alloc(e_end - e_begin)) return SF_ERR_HIP;
     sf::launch_pack_lu(p->d_Super, p->d_Lsip, p->d_Xp, p->d_Lsxp, (int32_t)p->nsuper, p->d_Lsx, p->d_Lsx + p->xC, tmp, e_begin, e_end, p->stream);
-    hipError_t e1 = hipGetLastError();
-    hipError_t e2 = hipMemcpyAsync(out, tmp, (e_end - e_begin) * sizeof(double), hipMemcpyDeviceToHost, p->stream);
-    hipError_t e3 = hipStreamSynchronize(p->stream);
-    (void)hipFree(tmp);
-    return (e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess) ? SF_OK : SF_ERR_HIP;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, tmp, (e_end - e_begin) * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return SF_OK;
 }
 
 int sf_plan_panel_hashes(sf_chol_plan* p, const uint64_t** out) {
@@ -1096,19 +1066,18 @@ int sf_plan_panel_hashes(sf_chol_plan* p, const uint64_t** out) {
     if (p->hash_epoch != p->epoch || p->h_hash.size() != (size_t)std::max<int64_t>(p->nsuper, 1)) {
         if (p->dry) return SF_ERR_ARG;        // a schedule-only plan has no device side
         HIP_TRY(hipSetDevice(p->device));
-        const size_t nb = (size_t)std::max<int64_t>(p->nsuper, 1) * sizeof(unsigned long long);
-        unsigned long long* d_h = nullptr;
-        HIP_TRY(hipMalloc((void**)&d_h, nb));
+        const size_t nh = (size_t)std::max<int64_t>(p->nsuper, 1), nb = nh * sizeof(unsigned long long);
+        sf::DevMem<unsigned long long> d_h;
+        if (d_h.alloc(nh)) return SF_ERR_HIP;
         const int64_t* xp = (p->lu || p->partial) ? p->d_Xp : p->d_Lsxp;
-        hipError_t e0 = hipMemsetAsync(d_h, 0, nb, p->stream);
+        p->hash_epoch = -1;     // (until the hashes have arrived)
+        HIP_TRY(hipMemsetAsync(d_h, 0, nb, p->stream));
         sf::launch_factor_hash(p->d_Super, p->d_Lsip, xp, p->d_Lsxp, (int32_t)p->nsuper, p->d_Lsx, p->d_Lsx + p->xC, p->lu ? 1 : 0,
                                p->xsize, d_h, p->stream);
-        hipError_t e1 = hipGetLastError();
-        p->h_hash.assign((size_t)std::max<int64_t>(p->nsuper, 1), 0);
-        hipError_t e2 = hipMemcpyAsync(p->h_hash.data(), d_h, nb, hipMemcpyDeviceToHost, p->stream);
-        hipError_t e3 = hipStreamSynchronize(p->stream);
-        (void)hipFree(d_h);
-        if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { p->hash_epoch = -1; return SF_ERR_HIP; }
+        HIP_TRY(hipGetLastError());
+        p->h_hash.assign(nh, 0);
+        HIP_TRY(hipMemcpyAsync(p->h_hash.data(), d_h, nb, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
         p->hash_epoch = p->epoch;
     }
     *out = p->h_hash.data();

@@ -202,7 +202,7 @@ int dio_values_done(sf_chol_plan* p) {
     if (p->lu) {
         // max |a_ij| from the device arrays: the scale of the pivot perturbation
         if (!p->d_dio_part)
-            if (int rc = sf_device_alloc((void**)&p->d_dio_part, 2 * (size_t)sf::DIO_MAXB * sizeof(double))) return rc;
+            if (int rc = p->d_dio_part.alloc(2 * (size_t)sf::DIO_MAXB)) return rc;
         std::vector<double> h(2 * sf::DIO_MAXB, 0.0);
         int nb[2] = {0, 0};
         const double* src[2] = {p->d_Lx, p->u_alias ? nullptr : p->d_Ux};
@@ -270,12 +270,15 @@ int sf_chol_plan_set_ordering(sf_chol_plan* p, const sf_long* perm) {
     if (!sf_plan_whole_resident(p)) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     const size_t bytes = h.size() * sizeof(int32_t);
-    if (!p->d_perm) {
-        if (int rc = sf_device_alloc((void**)&p->d_perm, bytes)) return rc;
+    sf::DevMem<int32_t> fresh;      // the first call's; the plan takes it once it is filled
+    if (!p->d_perm)
+        if (int rc = fresh.alloc(h.size())) return rc;
+    HIP_TRY(hipStreamSynchronize(p->stream));       // (nothing of an earlier call still reads the old ordering)
+    HIP_TRY(hipMemcpy(fresh ? fresh.get() : p->d_perm.get(), h.data(), bytes, hipMemcpyHostToDevice));
+    if (fresh) {
+        p->d_perm = std::move(fresh);
         p->bytes_ordering += bytes;
     }
-    HIP_TRY(hipStreamSynchronize(p->stream));       // (nothing of an earlier call still reads the old ordering)
-    HIP_TRY(hipMemcpy(p->d_perm, h.data(), bytes, hipMemcpyHostToDevice));
     return SF_OK;
 }
 int sf_lu_plan_set_ordering(sf_lu_plan* p, const sf_long* perm) { return (p && p->lu) ? sf_chol_plan_set_ordering(p, perm) : SF_ERR_ARG; }
@@ -338,13 +341,16 @@ int sf_chol_plan_set_value_map(sf_chol_plan* p, sf_long nsrc, const sf_long* map
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipStreamSynchronize(p->stream));
     const size_t nl = (size_t)std::max<int64_t>(p->nnz, 1), nu = need_u ? (size_t)p->unz : 0;
-    if (!p->d_vmap) {
-        const size_t bytes = (nl + nu) * sizeof(int64_t);
-        if (int rc = sf_device_alloc((void**)&p->d_vmap, bytes)) return rc;
-        p->bytes_ordering += bytes;
+    sf::DevMem<int64_t> fresh;      // the first call's; the plan takes it once it is filled
+    if (!p->d_vmap)
+        if (int rc = fresh.alloc(nl + nu)) return rc;
+    int64_t* vmap = fresh ? fresh.get() : p->d_vmap.get();
+    if (p->nnz > 0) HIP_TRY(hipMemcpy(vmap, mapL, (size_t)p->nnz * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (nu) HIP_TRY(hipMemcpy(vmap + nl, mapU, nu * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (fresh) {
+        p->d_vmap = std::move(fresh);
+        p->bytes_ordering += (nl + nu) * sizeof(int64_t);
     }
-    if (p->nnz > 0) HIP_TRY(hipMemcpy(p->d_vmap, mapL, (size_t)p->nnz * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (nu) HIP_TRY(hipMemcpy(p->d_vmap + nl, mapU, nu * sizeof(int64_t), hipMemcpyHostToDevice));
     p->vmap_nsrc = nsrc;
     return SF_OK;
 }

@@ -101,16 +101,12 @@ GramLayout gram_layout(int64_t n, int64_t nch) {
 int gram_store(sf_chol_plan* p, int64_t nch) {
     if (p->d_gram && p->gram_chunks >= nch) return SF_OK;
     const GramLayout L = gram_layout(p->n, nch);
-    const size_t bytes = (L.y + L.part + L.g) * sizeof(double);
-    double* fresh = nullptr;
-    if (hipMalloc((void**)&fresh, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return SF_ERR_ALLOC;
-    }
-    if (p->d_gram) (void)hipFree(p->d_gram);        // (every call returns with its work complete: nothing still reads it)
-    p->d_gram = fresh;
+    const size_t count = L.y + L.part + L.g;
+    sf::DevMem<double> fresh;
+    if (int rc = fresh.alloc(count)) return rc;
+    p->d_gram = std::move(fresh);       // (frees the smaller store: every call returns with its work complete, nothing still reads it)
     p->gram_chunks = nch;
-    p->bytes_gram = bytes;
+    p->bytes_gram = count * sizeof(double);
     return SF_OK;
 }
 

@@ -131,17 +131,13 @@ int lug_store(sf_chol_plan* p, int64_t nz, int64_t ny) {
     nz = std::max(nz, p->gram_chunks);
     ny = std::max(ny, p->gram_chunks_y);
     const Gram2Layout L = lug_layout(p->n, nz, ny);
-    const size_t bytes = (L.z + L.y + L.part + L.g) * sizeof(double);
-    double* fresh = nullptr;
-    if (hipMalloc((void**)&fresh, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return SF_ERR_ALLOC;
-    }
-    if (p->d_gram) (void)hipFree(p->d_gram);        // (every call returns with its work complete: nothing still reads it)
-    p->d_gram = fresh;
+    const size_t count = L.z + L.y + L.part + L.g;
+    sf::DevMem<double> fresh;
+    if (int rc = fresh.alloc(count)) return rc;
+    p->d_gram = std::move(fresh);       // (frees the smaller store: every call returns with its work complete, nothing still reads it)
     p->gram_chunks = nz;
     p->gram_chunks_y = ny;
-    p->bytes_gram = bytes;
+    p->bytes_gram = count * sizeof(double);
     return SF_OK;
 }
 

@@ -303,8 +303,7 @@ static void abort_comm(sf_comm* c) {
 // Returns my_rc if this rank failed, SF_ERR_PEER if only others did.
 static int agree_status(sf_chol_plan* p, sf_comm* comm, int my_rc, hipStream_t st) {
     if (comm->nranks == 1) return my_rc;
-    bool ok = hipSetDevice(p->device) == hipSuccess;
-    if (ok && !p->d_status) ok = hipMalloc((void**)&p->d_status, sizeof(double)) == hipSuccess;      // (plans made before round 4 only)
+    bool ok = p->d_status && hipSetDevice(p->device) == hipSuccess;      // (every plan of several ranks is created with its status word)
     double flag = my_rc ? 1.0 : 0.0, got = 1.0;
     ok = ok && hipMemcpyAsync(p->d_status, &flag, sizeof flag, hipMemcpyHostToDevice, st) == hipSuccess;
     int rc;
@@ -377,8 +376,8 @@ int sf_chol_plan_prepare_comm(sf_chol_plan* p, sf_comm* comm) {
     if (rc) return rc;
     if (p->dry) return SF_ERR_ARG;        // a schedule-only plan has no device side
     HIP_TRY(hipSetDevice(p->device));
-    double* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, sizeof(double)));
+    sf::DevMem<double> d;
+    if (d.alloc(1)) return SF_ERR_HIP;
     std::vector<sf_comm*> cs{comm};
     for (uint32_t m : p->all_masks)                  // ascending masks: every rank meets the groups it shares with another in one order
         if (sf_comm* g = group_comm(comm, m))
@@ -392,7 +391,6 @@ int sf_chol_plan_prepare_comm(sf_chol_plan* p, sf_comm* comm) {
             hipStreamSynchronize(p->stream) != hipSuccess) { rc = SF_ERR_HIP; break; }
         if (got != (double)c->nranks) { rc = SF_ERR_HIP; break; }
     }
-    (void)hipFree(d);
     return rc;
 }
 

@@ -337,26 +337,22 @@ static int layout_panels(const PlanInput& in, sf_chol_plan& p, Layout& lay) {
 // own while the calling one builds the task tables ... and, behind the allocation, the device copies of the symbolic structure
 // (narrowed to 32-bit indices on the way): 150 MB of host loops and pageable H2D copies at 128^3 that depend on the inputs only,
 // i.e. ~35 ms of the first call of a pattern that now run beside the validation and the task tables instead of after them (round 4).
-// The destructor joins the thread and frees whatever the plan has not taken over.
+// The destructor joins the thread; what the plan has not taken over by then goes with the owners.
 struct EarlyDevice {
     std::thread thread;
     hipError_t alloc_err = hipSuccess;
     size_t factor_bytes = 0;
     double* lent = nullptr;                 // the caller's buffer (sf_plan_offer_factor_buffer), if it is large enough
-    double* factor_mem = nullptr;           // handed to the plan once everything else has succeeded
-    int64_t *d_Lp = nullptr, *d_Lsip = nullptr, *d_Lsxp = nullptr;
-    int32_t *d_Li = nullptr, *d_Super = nullptr, *d_SuperMap = nullptr, *d_Lsi = nullptr;
+    sf::DevMem<double> factor_mem;          // handed to the plan once everything else has succeeded
+    sf::DevMem<int64_t> d_Lp, d_Lsip, d_Lsxp;
+    sf::DevMem<int32_t> d_Li, d_Super, d_SuperMap, d_Lsi;
     size_t bytes = 0;
     int rc = SF_OK;
 
     EarlyDevice() = default;
     EarlyDevice(const EarlyDevice&) = delete;
     void join() { if (thread.joinable()) thread.join(); }
-    ~EarlyDevice() {
-        join();
-        void* q[] = {factor_mem, d_Lp, d_Lsip, d_Lsxp, d_Li, d_Super, d_SuperMap, d_Lsi};
-        for (void* x : q) if (x) (void)hipFree(x);
-    }
+    ~EarlyDevice() { join(); }
     // takes this thread's factor-buffer offer (used or not) and starts the helper; a schedule-only plan starts nothing
     void start(const PlanInput& in, sf_chol_plan& p) {
         // + 2 doubles: the GEMM stages row PAIRS with 16-byte loads and may touch 8 bytes past the last panel.
@@ -367,16 +363,16 @@ struct EarlyDevice {
         if (in.dry) return;
         thread = std::thread([this, &in] {
             alloc_err = hipSetDevice(in.device);
-            if (alloc_err == hipSuccess && !lent) alloc_err = hipMalloc((void**)&factor_mem, factor_bytes);
+            if (alloc_err == hipSuccess && !lent && factor_mem.alloc(factor_bytes / sizeof(double))) alloc_err = hipErrorOutOfMemory;
             if (alloc_err != hipSuccess) return;
             auto narrow = [](const sf_long* a, sf_long len) { std::vector<int32_t> v((size_t)std::max<sf_long>(len, 0)); for (sf_long k = 0; k < len; ++k) v[(size_t)k] = (int32_t)a[k]; return v; };
-            if (!rc) rc = upload(&d_Lp, std::vector<int64_t>(in.Lp, in.Lp + in.n + 1), &bytes);
-            if (!rc) rc = upload(&d_Li, narrow(in.Li, in.Lp[in.n]), &bytes);
-            if (!rc) rc = upload(&d_Super, narrow(in.Super, in.nsuper + 1), &bytes);
-            if (!rc) rc = upload(&d_SuperMap, narrow(in.SuperMap, in.n), &bytes);
-            if (!rc) rc = upload(&d_Lsip, std::vector<int64_t>(in.Lsip, in.Lsip + in.nsuper + 1), &bytes);
-            if (!rc) rc = upload(&d_Lsi, narrow(in.Lsi, in.Lsip[in.nsuper]), &bytes);
-            if (!rc) rc = upload(&d_Lsxp, std::vector<int64_t>(in.Lsxp, in.Lsxp + in.nsuper + 1), &bytes);
+            if (!rc) rc = upload(d_Lp, std::vector<int64_t>(in.Lp, in.Lp + in.n + 1), &bytes);
+            if (!rc) rc = upload(d_Li, narrow(in.Li, in.Lp[in.n]), &bytes);
+            if (!rc) rc = upload(d_Super, narrow(in.Super, in.nsuper + 1), &bytes);
+            if (!rc) rc = upload(d_SuperMap, narrow(in.SuperMap, in.n), &bytes);
+            if (!rc) rc = upload(d_Lsip, std::vector<int64_t>(in.Lsip, in.Lsip + in.nsuper + 1), &bytes);
+            if (!rc) rc = upload(d_Lsi, narrow(in.Lsi, in.Lsip[in.nsuper]), &bytes);
+            if (!rc) rc = upload(d_Lsxp, std::vector<int64_t>(in.Lsxp, in.Lsxp + in.nsuper + 1), &bytes);
         });
     }
 };
@@ -1309,16 +1305,12 @@ static int create_device_resources(const PlanInput& in, const PlanKnobs& kn, con
     }
 
     // dry plans count the bytes a real plan would allocate and touch nothing
-    auto up = [&](auto** dptr, const auto& h) -> int {
-        if (!in.dry) return upload(dptr, h, &p.bytes_device);
-        *dptr = nullptr;
+    auto up = [&](auto& d, const auto& h) -> int {
+        if (!in.dry) return upload(d, h, &p.bytes_device);
         p.bytes_device += std::max<size_t>(h.size(), 1) * sizeof(typename std::decay_t<decltype(h)>::value_type);
         return SF_OK;
     };
-    auto dalloc = [&](void** ptr, size_t bytes) -> bool {
-        if (in.dry) { *ptr = nullptr; return true; }
-        return hipMalloc(ptr, bytes) == hipSuccess;
-    };
+    auto dalloc = [&](auto& d, size_t bytes) -> bool { return in.dry || d.alloc(bytes / sizeof(*d.get())) == SF_OK; };
     // The plan's streams are HIGH-PRIORITY streams: the runtime multiplexes all streams of one priority over a few hardware
     // queues (4 by default), and the copy-back workers bring six streams of their own.  Whenever the compute stream landed on
     // a hardware queue together with one of those, its kernels queued up behind the worker's event waits and copies and a
@@ -1332,18 +1324,18 @@ static int create_device_resources(const PlanInput& in, const PlanKnobs& kn, con
         (void)hipGetLastError();
         prio = false;
     }
-    auto new_stream = [&](hipStream_t* st, unsigned flags) {
-        if (prio && hipStreamCreateWithPriority(st, flags, prio_greatest) == hipSuccess) return true;
+    auto new_stream = [&](sf::Stream& st, unsigned flags) {
+        if (prio && hipStreamCreateWithPriority(st.put(), flags, prio_greatest) == hipSuccess) return true;
         (void)hipGetLastError();
-        return hipStreamCreateWithFlags(st, flags) == hipSuccess;
+        return hipStreamCreateWithFlags(st.put(), flags) == hipSuccess;
     };
-    if (!in.dry && (!new_stream(&p.stream, hipStreamDefault) || hipEventCreate(&p.ev0) != hipSuccess ||
-        hipEventCreate(&p.ev1) != hipSuccess || hipEventCreate(&p.ev_s0) != hipSuccess ||
-        hipEventCreate(&p.ev_s1) != hipSuccess)) return SF_ERR_HIP;
-    p.dl_events.assign(p.dl_ev_ready.size(), nullptr);
+    if (!in.dry && (!new_stream(p.stream, hipStreamDefault) || hipEventCreate(p.ev0.put()) != hipSuccess ||
+        hipEventCreate(p.ev1.put()) != hipSuccess || hipEventCreate(p.ev_s0.put()) != hipSuccess ||
+        hipEventCreate(p.ev_s1.put()) != hipSuccess)) return SF_ERR_HIP;
+    p.dl_events = std::vector<sf::Event>(p.dl_ev_ready.size());
     if (!in.dry) {
         bool ok = true;
-        for (hipEvent_t& e : p.dl_events) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventBlockingSync) == hipSuccess;    // the copy workers sleep on them
+        for (sf::Event& e : p.dl_events) ok = ok && hipEventCreateWithFlags(e.put(), hipEventDisableTiming | hipEventBlockingSync) == hipSuccess;    // the copy workers sleep on them
         if (!ok) return SF_ERR_HIP;
     }
     // the structure arrays were uploaded by the helper thread (behind the factor's allocation); a schedule-only plan counts them
@@ -1354,63 +1346,61 @@ static int create_device_resources(const PlanInput& in, const PlanKnobs& kn, con
         early.join();
         if (early.alloc_err != hipSuccess) { (void)hipGetLastError(); return SF_ERR_ALLOC; }
         if (early.rc) return early.rc;
-        p.d_Lp = early.d_Lp; p.d_Li = early.d_Li; p.d_Super = early.d_Super; p.d_SuperMap = early.d_SuperMap;
-        p.d_Lsip = early.d_Lsip; p.d_Lsi = early.d_Lsi; p.d_Lsxp = early.d_Lsxp;
-        early.d_Lp = early.d_Lsip = early.d_Lsxp = nullptr; early.d_Li = early.d_Super = early.d_SuperMap = early.d_Lsi = nullptr;
+        p.d_Lp = std::move(early.d_Lp); p.d_Li = std::move(early.d_Li); p.d_Super = std::move(early.d_Super);
+        p.d_SuperMap = std::move(early.d_SuperMap); p.d_Lsip = std::move(early.d_Lsip); p.d_Lsi = std::move(early.d_Lsi);
+        p.d_Lsxp = std::move(early.d_Lsxp);
         p.bytes_device += early.bytes;
     }
-    if (int rc = up(&p.d_potrf, T.potrf)) return rc;
-    if (int rc = up(&p.d_trsm, T.trsm)) return rc;
-    if (int rc = up(&p.d_steps, T.steps)) return rc;
+    if (int rc = up(p.d_potrf, T.potrf)) return rc;
+    if (int rc = up(p.d_trsm, T.trsm)) return rc;
+    if (int rc = up(p.d_steps, T.steps)) return rc;
     {
         p.n_flags = std::max<int32_t>(T.n_flags, 1);
         std::vector<int> zeros(std::max<int32_t>(T.n_flags, 1), 0);
-        if (int rc = up(&p.d_flags, zeros)) return rc;
+        if (int rc = up(p.d_flags, zeros)) return rc;
         const size_t tb = (size_t)std::max<int64_t>(T.max_diag_tasks, 1) * (in.lu ? 2048 : 1024) * sizeof(double);
-        if (!dalloc((void**)&p.d_tinv, tb)) return SF_ERR_ALLOC;
+        if (!dalloc(p.d_tinv, tb)) return SF_ERR_ALLOC;
         p.bytes_device += tb;
     }
-    if (int rc = up(&p.d_probs, T.probs)) return rc;
-    if (int rc = up(&p.d_gtasks, T.gtasks)) return rc;
-    if (int rc = up(&p.d_stasks, T.stasks)) return rc;
-    if (int rc = up(&p.d_ktprefix, T.ktprefix)) return rc;
+    if (int rc = up(p.d_probs, T.probs)) return rc;
+    if (int rc = up(p.d_gtasks, T.gtasks)) return rc;
+    if (int rc = up(p.d_stasks, T.stasks)) return rc;
+    if (int rc = up(p.d_ktprefix, T.ktprefix)) return rc;
     {   // relative maps of all Schur updates, built on the device (createRelativeMap, CK:42-60, once per plan)
         const size_t mb = (size_t)std::max<int64_t>(T.relmap_size, 1) * sizeof(int32_t);
-        if (!dalloc((void**)&p.d_relmap, mb)) return SF_ERR_ALLOC;
+        if (!dalloc(p.d_relmap, mb)) return SF_ERR_ALLOC;
         p.bytes_device += mb;
         if (!in.dry) {
             std::vector<GemmProb> firsts;
             firsts.reserve(T.scatter_probs.size());
             for (int64_t k : T.scatter_probs) firsts.push_back(T.probs[k]);
-            GemmProb* d_firsts = nullptr;
+            sf::DevMem<GemmProb> d_firsts;
             size_t dummy = 0;
-            if (int rc = upload(&d_firsts, firsts, &dummy)) return rc;
+            if (int rc = upload(d_firsts, firsts, &dummy)) return rc;
             sf::launch_build_relmaps(d_firsts, (int)firsts.size(), p.d_Lsi, p.d_relmap, p.stream);
-            const hipError_t e1 = hipStreamSynchronize(p.stream), e2 = hipGetLastError();
-            (void)hipFree(d_firsts);
-            if (e1 != hipSuccess || e2 != hipSuccess) return SF_ERR_HIP;
+            if (hipStreamSynchronize(p.stream) != hipSuccess || hipGetLastError() != hipSuccess) return SF_ERR_HIP;
         }
     }
     if (!T.solve.empty()) {
-        if (int rc = up(&p.d_solve, T.solve)) return rc;
+        if (int rc = up(p.d_solve, T.solve)) return rc;
         if (!T.solveT_list.empty()) {
-            if (int rc = up(&p.d_solveT_list, T.solveT_list)) return rc;
-            if (!dalloc((void**)&p.d_solveT, (size_t)T.solveT_size * sizeof(double))) return SF_ERR_ALLOC;
+            if (int rc = up(p.d_solveT_list, T.solveT_list)) return rc;
+            if (!dalloc(p.d_solveT, (size_t)T.solveT_size * sizeof(double))) return SF_ERR_ALLOC;
             p.bytes_device += (size_t)T.solveT_size * sizeof(double);
             p.n_solveT = (int64_t)T.solveT_list.size();
         }
         const size_t sb = sf_solve_sync(&p).bytes;      // (the block's layout: sf_solve.hip)
-        if (!dalloc((void**)&p.d_solve_sync, sb)) return SF_ERR_ALLOC;
+        if (!dalloc(p.d_solve_sync, sb)) return SF_ERR_ALLOC;
         p.bytes_device += sb;
-        if (!dalloc((void**)&p.d_x, std::max<int64_t>(in.n, 1) * sizeof(double))) return SF_ERR_ALLOC;
+        if (!dalloc(p.d_x, std::max<int64_t>(in.n, 1) * sizeof(double))) return SF_ERR_ALLOC;
         p.bytes_device += std::max<int64_t>(in.n, 1) * sizeof(double);
     }
     if (in.lu || p.partial) {
-        if (int rc = up(&p.d_Xp, lay.XP)) return rc;
+        if (int rc = up(p.d_Xp, lay.XP)) return rc;
     }
     if (!T.fill_tiles.empty()) {
         const size_t fb = T.fill_tiles.size() * sizeof(sf::FillTile);
-        if (!dalloc(&p.d_fill, fb)) return SF_ERR_ALLOC;
+        if (!dalloc(p.d_fill, fb)) return SF_ERR_ALLOC;
         if (!in.dry && hipMemcpy(p.d_fill, T.fill_tiles.data(), fb, hipMemcpyHostToDevice) != hipSuccess) return SF_ERR_HIP;
         p.bytes_device += fb;
     }
@@ -1421,20 +1411,20 @@ static int create_device_resources(const PlanInput& in, const PlanKnobs& kn, con
         bool any_owner = false;
         for (const Segment& sg : p.segments) any_owner = any_owner || sg.owner_gi >= 0;
         const size_t nbuf = any_owner ? 3 : 2;          // owner-computes: the broadcast has a buffer of its own (the next block's sum may be in flight)
-        if (!dalloc((void**)&p.d_scratch, nbuf * mx * sizeof(double))) return SF_ERR_ALLOC;
+        if (!dalloc(p.d_scratch, nbuf * mx * sizeof(double))) return SF_ERR_ALLOC;
         p.bytes_device += nbuf * mx * sizeof(double);
-        bool ok = in.dry || p.stream2 || new_stream(&p.stream2, hipStreamNonBlocking);
+        bool ok = in.dry || p.stream2 || new_stream(p.stream2, hipStreamNonBlocking);
         for (int k = 0; k < 2 && !in.dry; ++k) {
-            ok = ok && hipEventCreateWithFlags(&p.ev_contrib[k], hipEventDisableTiming) == hipSuccess;
-            ok = ok && hipEventCreateWithFlags(&p.ev_reduced[k], hipEventDisableTiming) == hipSuccess;
-            ok = ok && hipEventCreateWithFlags(&p.ev_unpacked[k], hipEventDisableTiming) == hipSuccess;
+            ok = ok && hipEventCreateWithFlags(p.ev_contrib[k].put(), hipEventDisableTiming) == hipSuccess;
+            ok = ok && hipEventCreateWithFlags(p.ev_reduced[k].put(), hipEventDisableTiming) == hipSuccess;
+            ok = ok && hipEventCreateWithFlags(p.ev_unpacked[k].put(), hipEventDisableTiming) == hipSuccess;
         }
         if (!ok) return SF_ERR_HIP;
     }
     if (in.nranks > 1) {
         // the word of the ranks' status agreement (sf_multi.hip, agree_status) exists from the start: the agreement itself must not
         // depend on an allocation that can fail on one rank alone
-        if (!dalloc((void**)&p.d_status, sizeof(double))) return SF_ERR_ALLOC;
+        if (!dalloc(p.d_status, sizeof(double))) return SF_ERR_ALLOC;
         p.bytes_device += sizeof(double);
     }
     if (in.ooc()) {
@@ -1444,7 +1434,7 @@ static int create_device_resources(const PlanInput& in, const PlanKnobs& kn, con
             const int unit = in.ooc_group[s] >= 0 ? in.ooc_group[s] : (in.ooc_top_mode >= 1 ? p.ooc_first[(size_t)s] : in.ooc_ngroups);
             mask[(size_t)unit * (size_t)in.nsuper + (size_t)s] = 1;
         }
-        if (int rc = up(&p.d_loadmask, mask)) return rc;
+        if (int rc = up(p.d_loadmask, mask)) return rc;
         if (in.ooc_top_mode >= 1) {        // what a group's first launch zeroes besides its buffer: the places of the top panels that start with it
             p.ooc_zero.assign((size_t)in.ooc_ngroups, {});
             for (sf_long s = 0; s < in.nsuper; ++s)
@@ -1461,21 +1451,21 @@ static int create_device_resources(const PlanInput& in, const PlanKnobs& kn, con
         // or on the rank the caller names (load_top 0 / 1: the older interface, one group of all ranks)
         for (sf_long s = 0; s < in.nsuper; ++s)
             mask[s] = (p.phase[s] == 0 || (p.phase[s] == 1 && (in.load_top == 2 ? lay.group_idx(lay.gmask[s]) == 0 : in.load_top != 0))) ? 1 : 0;
-        if (int rc = up(&p.d_loadmask, mask)) return rc;
+        if (int rc = up(p.d_loadmask, mask)) return rc;
     }
     if (in.lu) {
         // pivot records: pivpos | pivinv, n entries each, + the perturbation counter; identity until a factorization with
         // pivoting overwrites the blocks it interchanges
         const size_t pb = (size_t)(2 * std::max<int64_t>(in.n, 1) + 1) * sizeof(int32_t);
-        if (!dalloc((void**)&p.d_piv, pb)) return SF_ERR_ALLOC;
+        if (!dalloc(p.d_piv, pb)) return SF_ERR_ALLOC;
         p.bytes_device += pb;
         p.piv_tol = kn.piv_tol; p.piv_perturb = kn.piv_perturb;
         p.piv_tol0 = p.piv_tol; p.piv_perturb0 = p.piv_perturb;
         if (!p.u_alias) {
-            if (int rc = up(&p.d_Up, Up64)) return rc;
-            if (int rc = up(&p.d_Ui, Ui32)) return rc;
+            if (int rc = up(p.d_Up, Up64)) return rc;
+            if (int rc = up(p.d_Ui, Ui32)) return rc;
             const size_t ub = std::max<int64_t>(p.unz, 1) * sizeof(double);
-            if (!dalloc((void**)&p.d_Ux, ub)) return SF_ERR_ALLOC;
+            if (!dalloc(p.d_Ux, ub)) return SF_ERR_ALLOC;
             p.bytes_device += ub;
         }
     }
@@ -1484,13 +1474,13 @@ static int create_device_resources(const PlanInput& in, const PlanKnobs& kn, con
         // factorization.  Plans with assembly masks (several ranks, out of core) keep the searching kernel.
         const int64_t* xpm = in.lu ? p.d_Xp : p.d_Lsxp;
         const size_t mbL = (size_t)std::max<int64_t>(p.nnz, 1) * sizeof(int64_t);
-        if (!dalloc((void**)&p.d_loadmapL, mbL)) return SF_ERR_ALLOC;
+        if (!dalloc(p.d_loadmapL, mbL)) return SF_ERR_ALLOC;
         p.bytes_device += mbL;
         if (!in.dry) sf::launch_build_loadmap(p.d_Lp, p.d_Li, (int32_t)in.n, p.d_Super, p.d_SuperMap, p.d_Lsip, p.d_Lsi, xpm, 0, in.lu ? 1 : 0, p.d_loadmapL, p.stream);
         if (in.lu) {
             const int64_t nzu = p.u_alias ? p.nnz : p.unz;
             const size_t mbU = (size_t)std::max<int64_t>(nzu, 1) * sizeof(int64_t);
-            if (!dalloc((void**)&p.d_loadmapU, mbU)) return SF_ERR_ALLOC;
+            if (!dalloc(p.d_loadmapU, mbU)) return SF_ERR_ALLOC;
             p.bytes_device += mbU;
             if (!in.dry) sf::launch_build_loadmap(p.u_alias ? p.d_Lp : p.d_Up, p.u_alias ? p.d_Li : p.d_Ui, (int32_t)in.n, p.d_Super, p.d_SuperMap,
                                                p.d_Lsip, p.d_Lsi, xpm, p.xC, 0, p.d_loadmapU, p.stream);
@@ -1499,15 +1489,11 @@ static int create_device_resources(const PlanInput& in, const PlanKnobs& kn, con
             // (U aliasing L: the U map indexes the same entries as L's, so L's superseded positions are dropped from it too)
             const std::vector<int64_t>& drop = (u && !p.u_alias) ? p.load_dropU : p.load_dropL;
             if (drop.empty()) continue;
-            int64_t* d_drop = nullptr;
-            if (hipMalloc((void**)&d_drop, drop.size() * sizeof(int64_t)) != hipSuccess) return SF_ERR_ALLOC;
-            int rc = SF_OK;
-            if (hipMemcpy(d_drop, drop.data(), drop.size() * sizeof(int64_t), hipMemcpyHostToDevice) == hipSuccess)
-                sf::launch_loadmap_drop(d_drop, (int64_t)drop.size(), u ? p.d_loadmapU : p.d_loadmapL, p.stream);
-            else rc = SF_ERR_HIP;
-            if (hipStreamSynchronize(p.stream) != hipSuccess) rc = SF_ERR_HIP;
-            (void)hipFree(d_drop);
-            if (rc) return rc;
+            sf::DevMem<int64_t> d_drop;
+            if (int rc = d_drop.alloc(drop.size())) return rc;
+            const bool copied = hipMemcpy(d_drop, drop.data(), drop.size() * sizeof(int64_t), hipMemcpyHostToDevice) == hipSuccess;
+            if (copied) sf::launch_loadmap_drop(d_drop, (int64_t)drop.size(), u ? p.d_loadmapU.get() : p.d_loadmapL.get(), p.stream);
+            if (hipStreamSynchronize(p.stream) != hipSuccess || !copied) return SF_ERR_HIP;
         }
         if (!in.dry && (hipStreamSynchronize(p.stream) != hipSuccess || hipGetLastError() != hipSuccess)) return SF_ERR_HIP;
     }
@@ -1518,10 +1504,10 @@ static int create_device_resources(const PlanInput& in, const PlanKnobs& kn, con
     const size_t xb = early.factor_bytes, vb = std::max<int64_t>(p.nnz, 1) * sizeof(double);
     early.join();
     if (early.alloc_err != hipSuccess) { (void)hipGetLastError(); return SF_ERR_ALLOC; }
-    p.d_Lsx = early.lent ? early.lent : early.factor_mem;
-    early.factor_mem = nullptr;
-    if (!dalloc((void**)&p.d_Lx, vb) ||
-        !dalloc((void**)&p.d_info, (1 + p.n_tickets) * sizeof(int))) return SF_ERR_ALLOC;
+    if (early.lent) p.d_Lsx.lend(early.lent);
+    else p.d_Lsx = std::move(early.factor_mem);
+    if (!dalloc(p.d_Lx, vb) ||
+        !dalloc(p.d_info, (1 + p.n_tickets) * sizeof(int))) return SF_ERR_ALLOC;
     p.bytes_device += xb + vb + (1 + p.n_tickets) * sizeof(int);
     return SF_OK;
 }

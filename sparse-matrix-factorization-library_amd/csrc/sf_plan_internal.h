@@ -13,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "sf_device_mem.h"
 #include "sf_kernels.h"
 
 using sf::GemmProb;
@@ -70,13 +71,13 @@ struct Segment {
         }                                                                                   \
     } while (0)
 
+// h on the device (one element at least); bytes_total grows by its size.  A failed allocation is SF_ERR_HIP
 template <class T>
-static inline int upload(T** dptr, const std::vector<T>& h, size_t* bytes_total) {
-    *dptr = nullptr;
-    const size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
-    HIP_TRY(hipMalloc((void**)dptr, bytes));
-    if (!h.empty()) HIP_TRY(hipMemcpy(*dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    *bytes_total += bytes;
+static inline int upload(sf::DevMem<T>& d, const std::vector<T>& h, size_t* bytes_total) {
+    const size_t count = std::max<size_t>(h.size(), 1);
+    if (d.alloc(count)) return SF_ERR_HIP;
+    if (!h.empty()) HIP_TRY(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    *bytes_total += count * sizeof(T);
     return SF_OK;
 }
 
@@ -111,6 +112,8 @@ struct DlPiece {
 // struct path's device pool (sf_handlers.hip): the next plan_create of this thread may use `ptr` for its factor
 extern "C" void sf_plan_offer_factor_buffer(double* ptr, size_t bytes);
 extern "C" int sf_plan_factor_borrowed(const sf_chol_plan* p);
+// blocks that came through the seam of sf_device_mem.h and are still live in this process: 0 device, 1 pinned host
+extern "C" long sf_debug_live_blocks(int which);
 
 // hipEventElapsedTime whose failure (an event that was never recorded) is expected and must not stay behind as the thread's
 // "last error": callers that poll hipGetLastError after their own launches (PyTorch does) would report it as theirs
@@ -159,8 +162,6 @@ bool sf_device_ptr_ok(const sf_chol_plan* p, const void* ptr, size_t doubles);
 // it starts strictly inside the other)
 size_t sf_block_span(int64_t rows, sf_long cols, sf_long ld);
 bool sf_blocks_overlap(const void* a, size_t na, const void* b, size_t nb);
-// an allocation that is kept; a failure is SF_ERR_ALLOC, leaves *ptr null and no error behind in the runtime
-int sf_device_alloc(void** ptr, size_t bytes);
 // the n x SVM_W block d_xm with its staging half / the parts and results of launch_quadform, d_qf: allocated by whichever call
 // needs them first
 int sf_solve_many_block(sf_chol_plan* p);
@@ -205,35 +206,47 @@ struct SfApply {
 };
 // (the loop itself, a template on its two callables int(double* x, sf_long j0, int cw), follows the plan below)
 
-struct sf_chol_plan {
+// What a plan gives back AFTER its device memory, in this order: the graph, the events, stream2, the download's events, streams and
+// rings, the main stream last.  Members go in reverse order of declaration and a base after the members of the class derived
+// from it, so the order is written here once, backwards, and sf_chol_plan needs no list of what it holds.
+struct sf_plan_handles {
+    sf::Stream stream;                          // ours, or the caller's (own_stream, sf_chol_plan_set_stream)
+    sf::DevMem<double> d_ring;                  // LU: device staging of packed pieces, same shape as h_ring
+    sf::PinnedMem h_ring;                       // pinned staging ring: dl_workers x 2 slots of dl_slot doubles
+    sf::Event dl_done[DL_WORKERS_MAX][2];
+    sf::Stream dl_streams[DL_WORKERS_MAX];
+    std::vector<sf::Event> dl_events;
+    sf::Stream stream2;                         // the collectives of look-ahead segments and their pack copies
+    sf::Event ev_unpacked[2], ev_reduced[2], ev_contrib[2];
+    sf::Event ev_s1, ev_s0, ev1, ev0;
+    sf::GraphExec graph_exec;
+};
+
+struct sf_chol_plan : sf_plan_handles {
+    ~sf_chol_plan() { if (!dry) (void)hipSetDevice(device); }       // (the owners free on the plan's device)
     // ---- overlapped download schedule (built once) and the state of a running download ----
     std::vector<DlPiece> dl_pieces;
     std::vector<size_t> dl_ev_ready;            // launch count after which event k is recorded
-    std::vector<hipEvent_t> dl_events;
     bool dl_active = false;                     // run_launches records the events and publishes them
     size_t dl_next_ev = 0;
     std::mutex dl_mu;
     std::condition_variable dl_cv;
     size_t dl_published = 0;                    // events [0, dl_published) have been recorded (guarded by dl_mu)
     bool dl_abort = false;
-    double* h_ring = nullptr;                   // pinned staging ring: dl_workers x 2 slots of dl_slot doubles
-    double* d_ring = nullptr;                   // LU: device staging of packed pieces, same shape
     int64_t dl_slot = DL_SLOT_DEFAULT;
     int dl_workers = DL_WORKERS_DEFAULT;
     int dl_workers_fresh = DL_WORKERS_FRESH;    // ... when the destination's pages have never been touched (sf_dl_begin)
     int dl_workers_last = 0;                    // workers of the last download
-    hipStream_t dl_streams[DL_WORKERS_MAX] = {};
     // LU direct download: before a piece's event is recorded, the upper triangle (with the diagonal) of its columns' part of the
     // supernode's diagonal block is filled into the L panel from the U^T panel (k_lu_fill_u11), so that the L panel holds the
     // reference's packed L11 \ U11 and the download needs no gather kernel
     bool dl_host_wait = true;                   // copy workers wait for a piece's event on the host (see dl_worker)
     bool dl_lu_direct = false;
-    void* d_fill = nullptr;                     // sf::FillTile[], grouped by download event
+    sf::DevMem<sf::FillTile> d_fill;                  // sf::FillTile[], grouped by download event
     std::vector<int64_t> fill_first;            // tiles of event k: [fill_first[k], fill_first[k + 1])
     int dl_cpus_known = 0;                      // 0 not looked up yet, 1 dl_cpus holds the CPUs of the device's NUMA node, -1 none / disabled
     std::vector<int> dl_cpus;
     int dl_last_cpu[DL_WORKERS_MAX] = {};       // CPU each copy worker finished its last download on (SF_TRACE)
-    hipEvent_t dl_done[DL_WORKERS_MAX][2] = {};
     double last_to_host_ms = 0;                 // wall time of the last sf_chol_plan_factorize_to_host
     std::vector<std::thread> dl_threads;
     std::vector<double> dl_trace;               // SF_DL_TRACE: 3 times per piece
@@ -246,17 +259,17 @@ struct sf_chol_plan {
     // SparseFrame_set_pivoting (struct path) or SF_LU_PIVOT_TOL / SF_LU_PERTURB at plan creation
     double piv_tol = 0.0, piv_perturb = 0.0, amax = 0;
     double piv_tol0 = 0.0, piv_perturb0 = 0.0;      // the policy the plan was created with (environment or none): what a struct call without a policy of its own gets
-    int32_t* d_piv = nullptr;   // pivpos[n] | pivinv[n] | perturbation counter
+    sf::DevMem<int32_t> d_piv;   // pivpos[n] | pivinv[n] | perturbation counter
     int last_perturbed = 0;
     bool dry = false;           // schedule-only plan (plan_create's dry mode): no device resources, inspection only
     bool lu = false;            // no-pivot LU: every supernode has an L panel and a U^T panel (see plan_create)
     int64_t xC = 0;             // doubles in one set of nsrow x nscol panels (Cholesky: == xsize)
     int64_t unz = 0;            // LU: entries of U (by row)
-    int64_t* d_Up = nullptr;    // LU, unsymmetric input: U by row
-    int32_t* d_Ui = nullptr;
-    double* d_Ux = nullptr;
-    int64_t* d_Xp = nullptr;    // LU: offsets of the nsrow x nscol panels (the reference's Lsxp has the packed sizes)
-    double* d_pack = nullptr;   // LU: staging buffer in the reference layout for the download
+    sf::DevMem<int64_t> d_Up;    // LU, unsymmetric input: U by row
+    sf::DevMem<int32_t> d_Ui;
+    sf::DevMem<double> d_Ux;
+    sf::DevMem<int64_t> d_Xp;    // LU: offsets of the nsrow x nscol panels (the reference's Lsxp has the packed sizes)
+    sf::DevMem<double> d_pack;   // LU: staging buffer in the reference layout for the download
     bool u_alias = false;       // LU with a symmetric input: U aliases L (reference L:2718-2729)
     // multi-GPU sharding: phase[s] = 0 owned subtree supernode, 1 top supernode (replicated), -1 not on this rank
     std::vector<int8_t> phase;
@@ -268,12 +281,11 @@ struct sf_chol_plan {
     // pieces per group and how many of them are still on the device during a download
     // SF_GRAPH=1 (sf_chol_plan_factorize): the resident factorization as one hipGraph
     bool use_graph = false, capturing = false;
-    hipGraphExec_t graph_exec = nullptr;
     int graph_epoch = 0;
     int32_t n_flags = 1;
     double graph_tol = 0, graph_eps = 0;
     hipStream_t graph_stream = nullptr;
-    bool factor_borrowed = false;       // d_Lsx is a buffer the creator lent (sf_plan_offer_factor_buffer): never freed here
+    bool factor_borrowed = false;       // d_Lsx holds a buffer the creator lent (sf_plan_offer_factor_buffer, DevMem::lend)
     int ooc_groups = 0;
     int64_t ooc_buf = 0;
     // top mode 1 (active top panels only): first / last group below every top supernode, and per group the (offset, length) ranges its
@@ -286,27 +298,25 @@ struct sf_chol_plan {
     int rank = 0, nranks = 1;   // distributed top: this rank's share of the split launches
     std::vector<Segment> segments;
     std::vector<uint32_t> all_masks;    // every group of the factorization (all ranks build the same sorted list)
-    double* d_status = nullptr;    // one word: the ranks' status agreement before the first data collective (sf_multi.hip)
-    double* d_scratch = nullptr;   // packed segment buffers (2 x max over the segments: segment k uses half k & 1)
+    sf::DevMem<double> d_status;    // one word: the ranks' status agreement before the first data collective (sf_multi.hip)
+    sf::DevMem<double> d_scratch;   // packed segment buffers (2 x max over the segments: segment k uses half k & 1)
     int64_t scratch_elems = 0;
     bool top_owner = false;        // SF_TOP_OWNER=1: owner-computes chains for the sets every rank takes part in (prototype, see Segment)
     bool lookahead = true;         // shared top panels: outer GEMM split into a far part (ahead of the previous chain) and the last block's
-    hipStream_t stream2 = nullptr; // the collectives of look-ahead segments and their pack copies
-    hipEvent_t ev_contrib[2] = {nullptr, nullptr}, ev_reduced[2] = {nullptr, nullptr}, ev_unpacked[2] = {nullptr, nullptr};
     bool unpacked_recorded[2] = {false, false};
     int64_t packed_pending = -1;   // segment whose packed buffer has to be scattered back before it runs
     bool own_stream = true;
-    int8_t* d_loadmask = nullptr;
-    int64_t *d_loadmapL = nullptr, *d_loadmapU = nullptr;      // whole plans: offset into d_Lsx of every entry of L (/ U), -1 = not loaded
+    sf::DevMem<int8_t> d_loadmask;
+    sf::DevMem<int64_t> d_loadmapL, d_loadmapU;      // whole plans: offset into d_Lsx of every entry of L (/ U), -1 = not loaded
     std::vector<int64_t> load_dropL, load_dropU;   // entries given again later in their column (the last one is loaded): -1 in the load map
     // device solve (Cholesky, whole matrix on one device): task lists per (level, 64-column step)
-    sf::SolveTask* d_solve = nullptr;
+    sf::DevMem<sf::SolveTask> d_solve;
     // backward sweep: row-major copies of the diagonal blocks of the top levels' steps (made at the start of every solve)
-    double* d_solveT = nullptr;
-    int64_t* d_solveT_list = nullptr;
+    sf::DevMem<double> d_solveT;
+    sf::DevMem<int64_t> d_solveT_list;
     int64_t n_solveT = 0;
-    double* d_x = nullptr;
-    double* d_resid = nullptr;  // sf_chol_plan_validate: r | column sums | b | 4 norms
+    sf::DevMem<double> d_x;
+    sf::DevMem<double> d_resid;  // sf_chol_plan_validate: r | column sums | b | 4 norms
     // the forward launch of a step has fwd_count tasks, the backward one `count` (equal unless the plan is one rank's part of a
     // distributed factor: the forward tiles that update ancestors' rows are dealt out over the group, the backward ones are not);
     // big: a panel of the step is wider than 64 columns; red_first / red_count: sums over a group that precede the forward launch
@@ -316,36 +326,36 @@ struct sf_chol_plan {
     std::vector<SolveReduce> solve_reduces;
     std::vector<std::pair<int64_t, int64_t>> solve_own;           // column ranges whose solution this rank reports (distributed solve)
     std::vector<std::pair<int64_t, int64_t>> solve_load;          // column ranges whose right-hand side this rank loads
-    int* d_solve_sync = nullptr;
+    sf::DevMem<int> d_solve_sync;
     bool solve_bwd_fused = false;
     int n_solve_sync = 0;
     std::vector<SolveStep> solve_steps;
     double last_solve_ms = 0;
     // sf_chol_plan_solve_many: the n x SVM_W row-major block and an n x SVM_W column-major staging buffer for the copies, one
     // allocation made by the first call (not in bytes_device)
-    double* d_xm = nullptr;
+    sf::DevMem<double> d_xm;
     size_t bytes_solve_many = 0;
     double last_solve_many_ms = 0;
     // sf_chol_plan_solve_half / _quadform / _sample (sf_sample.hip): d_x or d_xm as above; d_qf = the parts and the results of the
     // per-column sums of squares, a fixed size allocated by the first quadform call (in no byte count)
-    double* d_qf = nullptr;
+    sf::DevMem<double> d_qf;
     double last_half_ms = 0, last_quadform_ms = 0, last_sample_ms = 0;
     // sf_chol_plan_gram / _gram_device (sf_gram.hip): the Y store -- gram_chunks row-major n x SVM_W blocks, the parts of one chunk
     // row, the result block of the host-array call -- allocated or grown by the first call that needs it (bytes_gram, not in
     // bytes_device); last_gram_parts: slabs per tile of the last call (0: the one-column path)
     // sf_lu_plan_gram / _gram_device (sf_gram_lu.hip): the same store holds gram_chunks Z blocks, gram_chunks_y Y blocks, the parts of
     // one chunk column and the padded result block
-    double* d_gram = nullptr;
+    sf::DevMem<double> d_gram;
     int64_t gram_chunks = 0, gram_chunks_y = 0;
     size_t bytes_gram = 0;
     double last_gram_ms = 0;
     int last_gram_parts = 0;
     // sf_*_plan_set_ordering / _set_value_map (sf_device_io.hip): perm[new] = old as 32-bit indices (as d_Lsi), the value map
     // (nnz entries for Lx, then unz for Ux) and the parts of the LU plans' max |a_ij|; bytes_ordering is not in bytes_device
-    int32_t* d_perm = nullptr;
-    int64_t* d_vmap = nullptr;
+    sf::DevMem<int32_t> d_perm;
+    sf::DevMem<int64_t> d_vmap;
     int64_t vmap_nsrc = 0;
-    double* d_dio_part = nullptr;
+    sf::DevMem<double> d_dio_part;
     size_t bytes_ordering = 0;
     // sf_chol_plan_selinv (sf_selinv.hip).  Generations of the factor: factor_gen moves whenever the values or the resident factor
     // change (set_values, the start of a factorization, an import); fact_gen = factor_gen of the last factorization started,
@@ -362,72 +372,70 @@ struct sf_chol_plan {
     std::vector<SelStep> sel_steps;
     std::vector<sf::SelPair> sel_pairs_h;
     int64_t sel_linv_elems = 0, sel_y_elems = 0, sel_z_elems = 0, sel_s_elems = 0;
-    double* d_sel = nullptr;            // the arena (xsize doubles), allocated with the scratch by the first call (not in bytes_device)
-    double* d_sel_diag = nullptr;
-    void* d_sel_units = nullptr;
-    void* d_sel_pairs = nullptr;
-    double* d_sel_scratch = nullptr;
+    sf::DevMem<double> d_sel;            // the arena (xsize doubles), allocated with the scratch by the first call (not in bytes_device)
+    sf::DevMem<double> d_sel_diag;
+    sf::DevMem<sf::SelUnit> d_sel_units;
+    sf::DevMem<sf::SelPair> d_sel_pairs;
+    sf::DevMem<double> d_sel_scratch;
     size_t bytes_selinv = 0;
     double last_selinv_ms = 0, flops_selinv = 0;
     // sf_*_plan_selinv_values / _trace / _entries (sf_selinv_pattern.hip): the position of every entry of the structure in one panel
     // set (posL, then posU of an LU plan with its own U structure) with the off-diagonal marks of a Cholesky plan, the parts and
     // results of a trace, the staging buffer of the (row, column) pairs -- each allocated by the first call that needs it
     // (bytes_selinv_pattern, not in bytes_device)
-    int64_t* d_sp_pos = nullptr;
-    uint8_t* d_sp_offd = nullptr;
-    double* d_sp_part = nullptr;
-    void* d_sp_stage = nullptr;
+    sf::DevMem<int64_t> d_sp_pos;
+    sf::DevMem<uint8_t> d_sp_offd;
+    sf::DevMem<double> d_sp_part;
+    sf::DevMem<char> d_sp_stage;
     size_t bytes_selinv_pattern = 0;
     double last_selinv_pattern_ms = 0;
     int64_t last_selinv_outside = 0;
     // sf_chol_plan_residual / sf_chol_plan_refine (sf_refine.hip): A by rows as positions into d_Lx / d_Ux (unsymmetric LU: also by
     // columns, for |A|_1), the vectors b | x | best x | r | w and the scalars; one set of allocations made by the first call
     // (not in bytes_device).  rf_anorm_gen = factor_gen the stored |A|_1 belongs to.
-    int64_t *d_rf_ptr = nullptr, *d_rf_pos = nullptr, *d_rf_cptr = nullptr, *d_rf_cpos = nullptr;
-    int32_t *d_rf_col = nullptr, *d_rf_ccol = nullptr;
-    double* d_rf_vec = nullptr;
+    sf::DevMem<int64_t> d_rf_ptr, d_rf_pos, d_rf_cptr, d_rf_cpos;
+    sf::DevMem<int32_t> d_rf_col, d_rf_ccol;
+    sf::DevMem<double> d_rf_vec;
     int64_t rf_entries = 0, rf_anorm_gen = -1;
     size_t bytes_refine = 0;
     int last_refine_iters = 0;
     double last_refine_berr0 = 0, last_refine_berr = 0, last_refine_ms = 0, last_residual_ms = 0;
     // sf_*_plan_condest (sf_solve_t.hip): x | the sign vector | the iteration's scalars, allocated by the first call (not in
     // bytes_device)
-    double* d_cond = nullptr;
+    sf::DevMem<double> d_cond;
     size_t bytes_condest = 0;
     int last_condest_solves = 0;
     double last_condest_ms = 0;
     int device = 0;
     int64_t n = 0, nsuper = 0, nnz = 0, isize = 0, xsize = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_s0 = nullptr, ev_s1 = nullptr;
 
     // device copies of the structure
-    int64_t* d_Lp = nullptr;
-    int32_t* d_Li = nullptr;
-    double* d_Lx = nullptr;
-    int32_t* d_Super = nullptr;
-    int32_t* d_SuperMap = nullptr;
-    int64_t* d_Lsip = nullptr;
-    int32_t* d_Lsi = nullptr;
-    int64_t* d_Lsxp = nullptr;
-    double* d_Lsx = nullptr;
-    int* d_info = nullptr;      // [0]: status bits of the running factorization; [1 ..]: task-claim counters of the k_step launches
+    sf::DevMem<int64_t> d_Lp;
+    sf::DevMem<int32_t> d_Li;
+    sf::DevMem<double> d_Lx;
+    sf::DevMem<int32_t> d_Super;
+    sf::DevMem<int32_t> d_SuperMap;
+    sf::DevMem<int64_t> d_Lsip;
+    sf::DevMem<int32_t> d_Lsi;
+    sf::DevMem<int64_t> d_Lsxp;
+    sf::DevMem<double> d_Lsx;
+    sf::DevMem<int> d_info;      // [0]: status bits of the running factorization; [1 ..]: task-claim counters of the k_step launches
     int n_tickets = 0;
     bool gemm_dynamic = true;   // k_gemm: whole-tile rounds claimed from per-XCD counters (SF_GEMM_DYNAMIC=0: static deal)
 
-    PotrfTask* d_potrf = nullptr;
-    TrsmTask* d_trsm = nullptr;
-    StepTask* d_steps = nullptr;
-    int* d_flags = nullptr;     // k_step: one flag per (panel, fused step); == epoch once its diagonal block is factored
-    double* d_tinv = nullptr;   // k_step: inverses of the 16 x 16 diagonal sub-blocks, per diagonal task of the running launch
+    sf::DevMem<PotrfTask> d_potrf;
+    sf::DevMem<TrsmTask> d_trsm;
+    sf::DevMem<StepTask> d_steps;
+    sf::DevMem<int> d_flags;     // k_step: one flag per (panel, fused step); == epoch once its diagonal block is factored
+    sf::DevMem<double> d_tinv;   // k_step: inverses of the 16 x 16 diagonal sub-blocks, per diagonal task of the running launch
     int epoch = 0;
     std::vector<uint64_t> h_hash;    // per-supernode fingerprints of the factor of epoch hash_epoch (sf_plan_panel_hashes)
     int hash_epoch = -1;
-    GemmProb* d_probs = nullptr;
-    GemmTask* d_gtasks = nullptr;
-    GemmTask* d_stasks = nullptr;   // tiles of k_update_small
-    uint32_t* d_ktprefix = nullptr;
-    int32_t* d_relmap = nullptr;
+    sf::DevMem<GemmProb> d_probs;
+    sf::DevMem<GemmTask> d_gtasks;
+    sf::DevMem<GemmTask> d_stasks;   // tiles of k_update_small
+    sf::DevMem<uint32_t> d_ktprefix;
+    sf::DevMem<int32_t> d_relmap;
 
     std::vector<Launch> launches;
     int nlevels = 0;

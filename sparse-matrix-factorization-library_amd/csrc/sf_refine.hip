@@ -148,7 +148,7 @@ bool refine_refused(const sf_chol_plan* p) {
 }
 
 template <class T>
-int fetch(std::vector<T>& h, const T* d, int64_t count) {
+int fetch(std::vector<T>& h, const typename std::vector<T>::value_type* d, int64_t count) {
     h.resize((size_t)std::max<int64_t>(count, 0));
     if (count > 0) HIP_TRY(hipMemcpy(h.data(), d, (size_t)count * sizeof(T), hipMemcpyDeviceToHost));
     return SF_OK;
@@ -183,22 +183,6 @@ void build_form(int64_t n, const std::vector<int64_t>& Dp, const std::vector<int
             if (Tlive[p] >= 0 && (keep_diag || Ti[p] != j)) { const int64_t i = Ti[p]; f.col[cur[i]] = (int32_t)j; f.pos[cur[i]++] = one_array ? p : ~p; }
 }
 
-struct DevAlloc {       // everything allocated by a failed set-up is released again
-    std::vector<void*> q;
-    size_t bytes = 0;
-    bool ok = true;
-    template <class T>
-    T* get(size_t count) {
-        void* d = nullptr;
-        const size_t b = std::max<size_t>(count, 1) * sizeof(T);
-        if (!ok || hipMalloc(&d, b) != hipSuccess) { (void)hipGetLastError(); ok = false; return nullptr; }
-        q.push_back(d);
-        bytes += b;
-        return (T*)d;
-    }
-    void release() { for (void* d : q) (void)hipFree(d); q.clear(); }
-};
-
 template <class T>
 bool put(T* d, const std::vector<T>& h, size_t count) {
     return count == 0 || hipMemcpy(d, h.data(), count * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
@@ -228,24 +212,26 @@ int refine_setup(sf_chol_plan* p) {
     } else {
         build_form(n, Lp, Li, liveL, Lp, Li, liveL, true, false, rows);
     }
-    DevAlloc a;
-    const size_t nr = (size_t)rows.ptr[n], nc = unsym ? (size_t)cols.ptr[n] : 0;
-    int64_t* rptr = a.get<int64_t>((size_t)n + 1);
-    int32_t* rcol = a.get<int32_t>(nr);
-    int64_t* rpos = a.get<int64_t>(nr);
-    int64_t* cptr = unsym ? a.get<int64_t>((size_t)n + 1) : nullptr;
-    int32_t* ccol = unsym ? a.get<int32_t>(nc) : nullptr;
-    int64_t* cpos = unsym ? a.get<int64_t>(nc) : nullptr;
-    double* vec = a.get<double>(5 * (size_t)std::max<int64_t>(n, 1) + RF_SCALARS);
-    if (!a.ok) { a.release(); return SF_ERR_ALLOC; }
-    bool ok = put(rptr, rows.ptr, (size_t)n + 1) && put(rcol, rows.col, nr) && put(rpos, rows.pos, nr);
-    if (unsym) ok = ok && put(cptr, cols.ptr, (size_t)n + 1) && put(ccol, cols.col, nc) && put(cpos, cols.pos, nc);
-    if (!ok) { (void)hipGetLastError(); a.release(); return SF_ERR_HIP; }
-    p->d_rf_ptr = rptr; p->d_rf_col = rcol; p->d_rf_pos = rpos;
-    p->d_rf_cptr = cptr; p->d_rf_ccol = ccol; p->d_rf_cpos = cpos;
-    p->d_rf_vec = vec;
+    const size_t nr = (size_t)rows.ptr[n], nc = unsym ? (size_t)cols.ptr[n] : 0, nv = 5 * (size_t)std::max<int64_t>(n, 1) + RF_SCALARS;
+    const size_t nr1 = std::max<size_t>(nr, 1), nc1 = std::max<size_t>(nc, 1);
+    sf::DevMem<int64_t> rptr, rpos, cptr, cpos;
+    sf::DevMem<int32_t> rcol, ccol;
+    sf::DevMem<double> vec;
+    size_t bytes = ((size_t)n + 1 + nr1) * sizeof(int64_t) + nr1 * sizeof(int32_t) + nv * sizeof(double);
+    if (rptr.alloc((size_t)n + 1) || rcol.alloc(nr1) || rpos.alloc(nr1)) return SF_ERR_ALLOC;
+    if (unsym) {
+        if (cptr.alloc((size_t)n + 1) || ccol.alloc(nc1) || cpos.alloc(nc1)) return SF_ERR_ALLOC;
+        bytes += ((size_t)n + 1 + nc1) * sizeof(int64_t) + nc1 * sizeof(int32_t);
+    }
+    if (vec.alloc(nv)) return SF_ERR_ALLOC;
+    bool ok = put(rptr.get(), rows.ptr, (size_t)n + 1) && put(rcol.get(), rows.col, nr) && put(rpos.get(), rows.pos, nr);
+    if (unsym) ok = ok && put(cptr.get(), cols.ptr, (size_t)n + 1) && put(ccol.get(), cols.col, nc) && put(cpos.get(), cols.pos, nc);
+    if (!ok) { (void)hipGetLastError(); return SF_ERR_HIP; }
+    p->d_rf_ptr = std::move(rptr); p->d_rf_col = std::move(rcol); p->d_rf_pos = std::move(rpos);
+    p->d_rf_cptr = std::move(cptr); p->d_rf_ccol = std::move(ccol); p->d_rf_cpos = std::move(cpos);
+    p->d_rf_vec = std::move(vec);
     p->rf_entries = (int64_t)nr;
-    p->bytes_refine = a.bytes;
+    p->bytes_refine = bytes;
     p->rf_anorm_gen = -1;
     return SF_OK;
 }

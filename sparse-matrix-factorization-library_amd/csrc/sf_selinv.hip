@@ -335,35 +335,6 @@ int sf_selinv_schedule(sf_chol_plan* p) {
 
 namespace {
 
-// arena + scratch; on failure everything allocated here is released and the plan is as before
-int selinv_alloc(sf_chol_plan* p) {
-    if (p->d_sel) return SF_OK;
-    const size_t nsm = std::max<size_t>(p->sel_small.size(), 1);
-    const size_t b_arena = (size_t)std::max<int64_t>(p->xsize, 1) * sizeof(double);
-    const size_t b_diag = (size_t)std::max<int64_t>(p->n, 1) * sizeof(double);
-    const size_t b_units = nsm * sizeof(SelUnit);
-    const size_t b_pairs = p->sel_pairs_h.size() * sizeof(sf::SelPair);
-    const size_t b_scr = (size_t)(p->sel_linv_elems + 2 * p->sel_y_elems + p->sel_z_elems + p->sel_s_elems + p->sel_linv_elems) * sizeof(double);
-    void* q[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t sz[5] = {b_arena, b_diag, b_units, b_pairs, b_scr};
-    for (int k = 0; k < 5; ++k) {
-        if (hipMalloc(&q[k], sz[k]) != hipSuccess) {
-            (void)hipGetLastError();
-            for (int t = 0; t < k; ++t) (void)hipFree(q[t]);
-            return SF_ERR_ALLOC;
-        }
-    }
-    p->d_sel = (double*)q[0];
-    p->d_sel_diag = (double*)q[1];
-    p->d_sel_units = (SelUnit*)q[2];
-    p->d_sel_pairs = (sf::SelPair*)q[3];
-    p->d_sel_scratch = (double*)q[4];
-    p->bytes_selinv = b_arena + b_diag + b_units + b_pairs + b_scr;
-    if (!p->sel_small.empty()) HIP_TRY(hipMemcpy(p->d_sel_units, p->sel_small.data(), b_units, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->d_sel_pairs, p->sel_pairs_h.data(), b_pairs, hipMemcpyHostToDevice));
-    return SF_OK;
-}
-
 template <int AM>
 void gemm(sf_chol_plan* p, int M, int N, int K, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
           int slabs, int64_t cstride, int acc_in, const SelUnit& u, hipStream_t st) {
@@ -408,32 +379,11 @@ extern "C" {
 
 int sf_chol_plan_selinv(sf_chol_plan* p) {
     if (!p || p->lu || !sf_plan_whole_resident(p)) return SF_ERR_ARG;
-    if (!sf_selinv_factor_current(p)) return SF_ERR_ARG;
-    if (p->n <= 0) return SF_OK;
-    HIP_TRY(hipSetDevice(p->device));
-    if (!p->sel_scheduled) {
-        const int rc = sf_selinv_schedule(p);
-        if (rc) return rc;
-    }
-    {
-        const int rc = selinv_alloc(p);
-        if (rc) return rc;
-    }
-    p->sel_gen = -1;
-    hipStream_t st = p->stream;
-    HIP_TRY(hipEventRecord(p->ev_s0, st));
-    for (const auto& s : p->sel_steps) {
-        for (int64_t k = s.big_first; k < s.big_first + s.big_count; ++k) run_big(p, p->sel_big[k], st);
-        sf::launch_selinv_small((const SelUnit*)p->d_sel_units + s.small_first, (int)s.small_count, p->d_Lsx, p->d_sel, sf::sel_struct(p), st);
-    }
-    HIP_TRY(hipEventRecord(p->ev_s1, st));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, p->ev_s0, p->ev_s1) == hipSuccess) p->last_selinv_ms = ms;
-    (void)hipGetLastError();
-    p->sel_gen = p->factor_gen;
-    return SF_OK;
+    return sf_selinv_run(
+        p, (size_t)std::max<int64_t>(p->xsize, 1),
+        [p] { return (size_t)(2 * p->sel_linv_elems + 2 * p->sel_y_elems + p->sel_z_elems + p->sel_s_elems); },
+        [p](const sf_chol_plan::SelBig& b, hipStream_t st) { run_big(p, b, st); },
+        [p](const SelUnit* units, int count, hipStream_t st) { sf::launch_selinv_small(units, count, p->d_Lsx, p->d_sel, sf::sel_struct(p), st); });
 }
 
 int sf_chol_plan_get_selinv_range(sf_chol_plan* p, sf_long e_begin, sf_long e_end, sf_float* out) {
@@ -448,14 +398,7 @@ int sf_chol_plan_get_selinv_range(sf_chol_plan* p, sf_long e_begin, sf_long e_en
 
 int sf_chol_plan_selinv_diag(sf_chol_plan* p, sf_float* d) {
     if (!p || p->lu || !sf_plan_whole_resident(p) || (!d && p->n > 0)) return SF_ERR_ARG;
-    if (p->n <= 0) return SF_OK;
-    if (!p->d_sel || p->sel_gen != p->factor_gen) return SF_ERR_ARG;
-    HIP_TRY(hipSetDevice(p->device));
-    sf::launch_selinv_diag((int64_t)p->n, p->d_sel, sf::sel_struct(p), p->d_sel_diag, p->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(d, p->d_sel_diag, (size_t)p->n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    return SF_OK;
+    return sf_selinv_diag_run(p, d, sf::launch_selinv_diag);
 }
 
 int sf_chol_plan_logdet(sf_chol_plan* p, sf_float* out) {
@@ -465,14 +408,13 @@ int sf_chol_plan_logdet(sf_chol_plan* p, sf_float* out) {
     if (p->n <= 0) return SF_OK;
     HIP_TRY(hipSetDevice(p->device));
     const int64_t nb = (p->n + 255) / 256;
-    double* buf = nullptr;
-    HIP_TRY(hipMalloc((void**)&buf, (size_t)(nb + 1) * sizeof(double)));
+    sf::DevMem<double> buf;
+    if (buf.alloc((size_t)nb + 1)) return SF_ERR_HIP;
     sf::launch_logdet((int64_t)p->n, p->d_Lsx, sf::sel_struct(p), buf, p->stream);
-    const hipError_t e1 = hipGetLastError();
-    const hipError_t e2 = hipMemcpyAsync(out, buf + nb, sizeof(double), hipMemcpyDeviceToHost, p->stream);
-    const hipError_t e3 = hipStreamSynchronize(p->stream);
-    (void)hipFree(buf);
-    return (e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess) ? SF_OK : SF_ERR_HIP;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, buf + nb, sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return SF_OK;
 }
 
 }  // extern "C"

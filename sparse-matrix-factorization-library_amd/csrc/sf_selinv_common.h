@@ -151,7 +151,7 @@ static inline void selinv_gemm(int M, int N, int K, const double* A, int64_t lda
 
 // the plan's structure arrays as the launchers take them
 static inline SelStruct sel_struct(const sf_chol_plan* p) {
-    return SelStruct{p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, p->lu ? p->d_Xp : p->d_Lsxp, (const SelPair*)p->d_sel_pairs, p->d_relmap};
+    return SelStruct{p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, p->lu ? p->d_Xp : p->d_Lsxp, p->d_sel_pairs, p->d_relmap};
 }
 
 }  // namespace sf
@@ -161,3 +161,64 @@ static inline SelStruct sel_struct(const sf_chol_plan* p) {
 bool sf_selinv_factor_current(sf_chol_plan* p);
 // the schedule (first call): units, pair table, scratch sizes, flops_selinv (an LU unit costs twice a Cholesky one)
 int sf_selinv_schedule(sf_chol_plan* p);
+
+// ---- the host driver both plans share ----
+// The state of the first call: the arena (`arena` doubles), the diagonal, the narrow units, the pair table and the scratch of the
+// wide units (`scratch` doubles).  A failure leaves the plan as it was.
+static inline int sf_selinv_alloc(sf_chol_plan* p, size_t arena, size_t scratch) {
+    if (p->d_sel) return SF_OK;
+    const size_t ndiag = (size_t)std::max<int64_t>(p->n, 1), nunits = std::max<size_t>(p->sel_small.size(), 1), npairs = p->sel_pairs_h.size();
+    sf::DevMem<double> sel, diag, scr;
+    sf::DevMem<sf::SelUnit> units;
+    sf::DevMem<sf::SelPair> pairs;
+    if (sel.alloc(arena) || diag.alloc(ndiag) || units.alloc(nunits) || pairs.alloc(npairs) || scr.alloc(scratch)) return SF_ERR_ALLOC;
+    if (!p->sel_small.empty()) HIP_TRY(hipMemcpy(units, p->sel_small.data(), nunits * sizeof(sf::SelUnit), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pairs, p->sel_pairs_h.data(), npairs * sizeof(sf::SelPair), hipMemcpyHostToDevice));
+    p->d_sel = std::move(sel);
+    p->d_sel_diag = std::move(diag);
+    p->d_sel_units = std::move(units);
+    p->d_sel_pairs = std::move(pairs);
+    p->d_sel_scratch = std::move(scr);
+    p->bytes_selinv = (arena + ndiag + scratch) * sizeof(double) + nunits * sizeof(sf::SelUnit) + npairs * sizeof(sf::SelPair);
+    return SF_OK;
+}
+
+// The selected inversion of a plan the entry point has accepted: the schedule and the allocations of a first call, then level by
+// level the big units (big(unit, stream), in list order) and the level's narrow supernodes in one launch (small(units, count, stream)).
+// scratch(): doubles of scratch, asked once the schedule is known.
+template <class Scratch, class Big, class Small>
+int sf_selinv_run(sf_chol_plan* p, size_t arena, Scratch&& scratch, Big&& big, Small&& small) {
+    if (!sf_selinv_factor_current(p)) return SF_ERR_ARG;
+    if (p->n <= 0) return SF_OK;
+    HIP_TRY(hipSetDevice(p->device));
+    if (!p->sel_scheduled)
+        if (int rc = sf_selinv_schedule(p)) return rc;
+    if (int rc = sf_selinv_alloc(p, arena, scratch())) return rc;
+    p->sel_gen = -1;
+    hipStream_t st = p->stream;
+    HIP_TRY(hipEventRecord(p->ev_s0, st));
+    for (const auto& s : p->sel_steps) {
+        for (int64_t k = s.big_first; k < s.big_first + s.big_count; ++k) big(p->sel_big[k], st);
+        small(p->d_sel_units + s.small_first, (int)s.small_count, st);
+    }
+    HIP_TRY(hipEventRecord(p->ev_s1, st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0;
+    if (elapsed_ms(&ms, p->ev_s0, p->ev_s1)) p->last_selinv_ms = ms;
+    p->sel_gen = p->factor_gen;
+    return SF_OK;
+}
+
+// diag(Sigma) of an accepted plan to the host, through `launch` (launch_selinv_diag or its LU twin)
+static inline int sf_selinv_diag_run(sf_chol_plan* p, sf_float* d,
+                                     void (*launch)(int64_t, const double*, const sf::SelStruct&, double*, hipStream_t)) {
+    if (p->n <= 0) return SF_OK;
+    if (!p->d_sel || p->sel_gen != p->factor_gen) return SF_ERR_ARG;
+    HIP_TRY(hipSetDevice(p->device));
+    launch((int64_t)p->n, p->d_sel, sf::sel_struct(p), p->d_sel_diag, p->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(d, p->d_sel_diag, (size_t)p->n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return SF_OK;
+}

@@ -314,36 +314,6 @@ LuScratch lu_scratch(const sf_chol_plan* p) {
     return s;
 }
 
-// both arenas (one allocation: SL, then SU xC doubles later) + scratch; on failure everything allocated here is released and the
-// plan is as before
-int lu_selinv_alloc(sf_chol_plan* p) {
-    if (p->d_sel) return SF_OK;
-    const size_t nsm = std::max<size_t>(p->sel_small.size(), 1);
-    const size_t b_arena = (size_t)std::max<int64_t>(2 * p->xC, 1) * sizeof(double);
-    const size_t b_diag = (size_t)std::max<int64_t>(p->n, 1) * sizeof(double);
-    const size_t b_units = nsm * sizeof(SelUnit);
-    const size_t b_pairs = p->sel_pairs_h.size() * sizeof(sf::SelPair);
-    const size_t b_scr = (size_t)(3 * p->sel_linv_elems + 4 * p->sel_y_elems + p->sel_z_elems + p->sel_s_elems) * sizeof(double);
-    void* q[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t sz[5] = {b_arena, b_diag, b_units, b_pairs, b_scr};
-    for (int k = 0; k < 5; ++k) {
-        if (hipMalloc(&q[k], sz[k]) != hipSuccess) {
-            (void)hipGetLastError();
-            for (int t = 0; t < k; ++t) (void)hipFree(q[t]);
-            return SF_ERR_ALLOC;
-        }
-    }
-    p->d_sel = (double*)q[0];
-    p->d_sel_diag = (double*)q[1];
-    p->d_sel_units = (SelUnit*)q[2];
-    p->d_sel_pairs = (sf::SelPair*)q[3];
-    p->d_sel_scratch = (double*)q[4];
-    p->bytes_selinv = b_arena + b_diag + b_units + b_pairs + b_scr;
-    if (!p->sel_small.empty()) HIP_TRY(hipMemcpy(p->d_sel_units, p->sel_small.data(), b_units, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->d_sel_pairs, p->sel_pairs_h.data(), b_pairs, hipMemcpyHostToDevice));
-    return SF_OK;
-}
-
 // Z = op(G) Y over the unit's R rows: (S, S2) = (SL, SU) for G, (SU, SL) for G^T; K slabs summed in a fixed order
 void gathered_product(sf_chol_plan* p, const sf_chol_plan::SelBig& b, const double* S, const double* S2, const double* Y, double* Z,
                       double* Zsl, hipStream_t st) {
@@ -408,32 +378,14 @@ extern "C" {
 
 int sf_lu_plan_selinv(sf_lu_plan* p) {
     if (!p || !p->lu || !sf_plan_whole_resident(p) || p->piv_tol > 0.0) return SF_ERR_ARG;
-    if (!sf_selinv_factor_current(p)) return SF_ERR_ARG;
-    if (p->n <= 0) return SF_OK;
-    HIP_TRY(hipSetDevice(p->device));
-    if (!p->sel_scheduled) {
-        const int rc = sf_selinv_schedule(p);
-        if (rc) return rc;
-    }
-    {
-        const int rc = lu_selinv_alloc(p);
-        if (rc) return rc;
-    }
-    p->sel_gen = -1;
-    hipStream_t st = p->stream;
-    HIP_TRY(hipEventRecord(p->ev_s0, st));
-    for (const auto& s : p->sel_steps) {
-        for (int64_t k = s.big_first; k < s.big_first + s.big_count; ++k) run_big(p, p->sel_big[k], st);
-        sf::launch_lu_selinv_small((const SelUnit*)p->d_sel_units + s.small_first, (int)s.small_count, p->d_Lsx, p->d_Lsx + p->xC, p->d_sel,
-                                   p->d_sel + p->xC, sf::sel_struct(p), st);
-    }
-    HIP_TRY(hipEventRecord(p->ev_s1, st));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0;
-    if (elapsed_ms(&ms, p->ev_s0, p->ev_s1)) p->last_selinv_ms = ms;
-    p->sel_gen = p->factor_gen;
-    return SF_OK;
+    // both arenas in one allocation: SL, then SU xC doubles later
+    return sf_selinv_run(
+        p, (size_t)std::max<int64_t>(2 * p->xC, 1),
+        [p] { return (size_t)(3 * p->sel_linv_elems + 4 * p->sel_y_elems + p->sel_z_elems + p->sel_s_elems); },
+        [p](const sf_chol_plan::SelBig& b, hipStream_t st) { run_big(p, b, st); },
+        [p](const SelUnit* units, int count, hipStream_t st) {
+            sf::launch_lu_selinv_small(units, count, p->d_Lsx, p->d_Lsx + p->xC, p->d_sel, p->d_sel + p->xC, sf::sel_struct(p), st);
+        });
 }
 
 int sf_lu_plan_get_selinv_range(sf_lu_plan* p, sf_long e_begin, sf_long e_end, sf_float* out) {
@@ -442,30 +394,19 @@ int sf_lu_plan_get_selinv_range(sf_lu_plan* p, sf_long e_begin, sf_long e_end, s
     if (e_end == e_begin) return SF_OK;
     HIP_TRY(hipSetDevice(p->device));
     const int64_t count = e_end - e_begin;
-    double* tmp = nullptr;
-    if (hipMalloc((void**)&tmp, (size_t)count * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        return SF_ERR_ALLOC;
-    }
+    sf::DevMem<double> tmp;
+    if (int rc = tmp.alloc((size_t)count)) return rc;
     sf::launch_lu_selinv_pack(sf::sel_struct(p), p->d_Lsxp, (int32_t)p->nsuper, p->d_sel, p->d_sel + p->xC, tmp, (int64_t)e_begin,
                               (int64_t)e_end, p->stream);
-    const hipError_t e1 = hipGetLastError();
-    const hipError_t e2 = hipMemcpyAsync(out, tmp, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, p->stream);
-    const hipError_t e3 = hipStreamSynchronize(p->stream);
-    (void)hipFree(tmp);
-    return (e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess) ? SF_OK : SF_ERR_HIP;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, tmp, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return SF_OK;
 }
 
 int sf_lu_plan_selinv_diag(sf_lu_plan* p, sf_float* d) {
     if (!p || !p->lu || !sf_plan_whole_resident(p) || (!d && p->n > 0)) return SF_ERR_ARG;
-    if (p->n <= 0) return SF_OK;
-    if (!p->d_sel || p->sel_gen != p->factor_gen) return SF_ERR_ARG;
-    HIP_TRY(hipSetDevice(p->device));
-    sf::launch_lu_selinv_diag((int64_t)p->n, p->d_sel, sf::sel_struct(p), p->d_sel_diag, p->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(d, p->d_sel_diag, (size_t)p->n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    return SF_OK;
+    return sf_selinv_diag_run(p, d, sf::launch_lu_selinv_diag);
 }
 
 int sf_lu_plan_logdet(sf_lu_plan* p, sf_float* logabs, int* sign) {
@@ -477,16 +418,14 @@ int sf_lu_plan_logdet(sf_lu_plan* p, sf_float* logabs, int* sign) {
     HIP_TRY(hipSetDevice(p->device));
     const int64_t nb = (p->n + 255) / 256;
     // partial sums | result (2 doubles) | partial counts
-    double* buf = nullptr;
-    HIP_TRY(hipMalloc((void**)&buf, (size_t)(nb + 2) * sizeof(double) + (size_t)nb * sizeof(int32_t)));
+    sf::DevMem<double> buf;
+    if (buf.alloc((size_t)(nb + 2) + (size_t)(nb + 1) / 2)) return SF_ERR_HIP;
     int32_t* neg = (int32_t*)(buf + nb + 2);
     double res[2] = {0.0, 0.0};
     sf::launch_lu_logdet((int64_t)p->n, p->d_Lsx + p->xC, sf::sel_struct(p), buf, neg, p->stream);
-    const hipError_t e1 = hipGetLastError();
-    const hipError_t e2 = hipMemcpyAsync(res, buf + nb, 2 * sizeof(double), hipMemcpyDeviceToHost, p->stream);
-    const hipError_t e3 = hipStreamSynchronize(p->stream);
-    (void)hipFree(buf);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return SF_ERR_HIP;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(res, buf + nb, 2 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
     *logabs = res[0];
     if (sign) {
         int sg = res[1] != 0.0 ? -1 : 1;

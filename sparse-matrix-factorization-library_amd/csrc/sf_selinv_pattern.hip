@@ -240,25 +240,18 @@ int selpat_positions(sf_chol_plan* p) {
     const bool own_u = p->lu && !p->u_alias;
     const size_t nl = (size_t)std::max<int64_t>(p->nnz, 1), nu = own_u ? (size_t)std::max<int64_t>(p->unz, 1) : 0;
     const size_t b_pos = (nl + nu) * sizeof(int64_t), b_off = p->lu ? 0 : nl;
-    int64_t* pos = nullptr;
-    uint8_t* offd = nullptr;
-    if (int rc = sf_device_alloc((void**)&pos, b_pos)) return rc;
+    sf::DevMem<int64_t> pos;
+    sf::DevMem<uint8_t> offd;
+    if (int rc = pos.alloc(nl + nu)) return rc;
     if (b_off)
-        if (int rc = sf_device_alloc((void**)&offd, b_off)) {
-            (void)hipFree(pos);
-            return rc;
-        }
+        if (int rc = offd.alloc(b_off)) return rc;
     const int64_t* xp = p->lu ? p->d_Xp : p->d_Lsxp;
     sf::launch_selpat_build(p->d_Lp, p->d_Li, (int32_t)p->n, p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, xp, pos, offd, p->stream);
     if (own_u)
         sf::launch_selpat_build(p->d_Up, p->d_Ui, (int32_t)p->n, p->d_Super, p->d_SuperMap, p->d_Lsip, p->d_Lsi, xp, pos + nl, nullptr, p->stream);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(p->stream) != hipSuccess) {
-        (void)hipFree(pos);
-        if (offd) (void)hipFree(offd);
-        return SF_ERR_HIP;
-    }
-    p->d_sp_pos = pos;
-    p->d_sp_offd = offd;
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(p->stream) != hipSuccess) return SF_ERR_HIP;
+    p->d_sp_pos = std::move(pos);
+    p->d_sp_offd = std::move(offd);
     p->bytes_selinv_pattern += b_pos + b_off;
     return SF_OK;
 }
@@ -267,9 +260,8 @@ int selpat_positions(sf_chol_plan* p) {
 int selpat_parts(sf_chol_plan* p) {
     if (p->d_sp_part) return SF_OK;
     const size_t np = (size_t)std::max<int64_t>(tiles(p->nnz) + tiles(u_count(p)), 1);
-    const size_t bytes = (np + 1) * sf::SELPAT_MAX_M * sizeof(double);
-    if (int rc = sf_device_alloc((void**)&p->d_sp_part, bytes)) return rc;
-    p->bytes_selinv_pattern += bytes;
+    if (int rc = p->d_sp_part.alloc((np + 1) * sf::SELPAT_MAX_M)) return rc;
+    p->bytes_selinv_pattern += (np + 1) * sf::SELPAT_MAX_M * sizeof(double);
     return SF_OK;
 }
 
@@ -277,7 +269,7 @@ int selpat_parts(sf_chol_plan* p) {
 int selpat_stage(sf_chol_plan* p) {
     if (p->d_sp_stage) return SF_OK;
     const size_t bytes = (size_t)sf::SELPAT_ENT_CHUNK * 3 * 8 + 8;
-    if (int rc = sf_device_alloc((void**)&p->d_sp_stage, bytes)) return rc;
+    if (int rc = p->d_sp_stage.alloc(bytes)) return rc;
     p->bytes_selinv_pattern += bytes;
     return SF_OK;
 }
@@ -307,16 +299,12 @@ int values_run(sf_chol_plan* p, bool transposed, double* dL, double* dU) {
 int values_host(sf_chol_plan* p, bool transposed, double* outL, double* outU) {
     const int64_t nl = p->nnz, nu = outU ? p->unz : 0;
     if (nl + nu <= 0) return SF_OK;
-    double* tmp = nullptr;
-    if (int rc = sf_device_alloc((void**)&tmp, (size_t)(nl + nu) * sizeof(double))) return rc;
-    int rc = values_run(p, transposed, tmp, nu > 0 ? tmp + nl : nullptr);
-    if (!rc) {
-        hipError_t e = nl > 0 ? hipMemcpy(outL, tmp, (size_t)nl * sizeof(double), hipMemcpyDeviceToHost) : hipSuccess;
-        if (e == hipSuccess && nu > 0) e = hipMemcpy(outU, tmp + nl, (size_t)nu * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = SF_ERR_HIP;
-    }
-    (void)hipFree(tmp);
-    return rc;
+    sf::DevMem<double> tmp;
+    if (int rc = tmp.alloc((size_t)(nl + nu))) return rc;
+    if (int rc = values_run(p, transposed, tmp, nu > 0 ? tmp + nl : nullptr)) return rc;
+    if (nl > 0 && hipMemcpy(outL, tmp, (size_t)nl * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return SF_ERR_HIP;
+    if (nu > 0 && hipMemcpy(outU, tmp + nl, (size_t)nu * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return SF_ERR_HIP;
+    return SF_OK;
 }
 
 int values_entry(sf_chol_plan* p, bool lu, bool dev, bool transposed, double* outL, double* outU) {
@@ -378,15 +366,13 @@ int trace_run(sf_chol_plan* p, bool mapped, int m, const double* VL, int64_t ldv
 }
 
 // a host block of m columns of `rows` doubles, ld apart, into fresh device memory (leading dimension rows)
-int upload_block(const double* V, int64_t rows, int64_t ld, int m, double** d) {
-    *d = nullptr;
-    if (int rc = sf_device_alloc((void**)d, (size_t)std::max<int64_t>(rows * m, 1) * sizeof(double))) return rc;
+int upload_block(const double* V, int64_t rows, int64_t ld, int m, sf::DevMem<double>& d) {
+    if (int rc = d.alloc((size_t)std::max<int64_t>(rows * m, 1))) return rc;
     if (rows <= 0) return SF_OK;
     const size_t col = (size_t)rows * sizeof(double);
-    if (hipMemcpy2D(*d, col, V, (size_t)ld * sizeof(double), col, m, hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMemcpy2D(d, col, V, (size_t)ld * sizeof(double), col, m, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(*d);
-        *d = nullptr;
+        d.reset();
         return SF_ERR_HIP;
     }
     return SF_OK;
@@ -411,15 +397,14 @@ int trace_entry(sf_chol_plan* p, bool lu, bool dev, sf_long m, const double* VL,
         if ((sl && !sf_device_ptr_ok(p, VL, sl)) || (su && !sf_device_ptr_ok(p, VU, su)) || !sf_device_ptr_ok(p, out, (size_t)m)) return SF_ERR_ARG;
         return trace_run(p, mapped, mi, VL, ldvl, need_u ? VU : nullptr, ldvu, out, nullptr);
     }
-    double *dL = nullptr, *dU = nullptr;
-    int rc = upload_block(VL, rows_l, ldvl, mi, &dL);
-    if (!rc && need_u) rc = upload_block(VU, rows_u, ldvu, mi, &dU);
+    sf::DevMem<double> dL, dU;
+    if (int rc = upload_block(VL, rows_l, ldvl, mi, dL)) return rc;
+    if (need_u)
+        if (int rc = upload_block(VU, rows_u, ldvu, mi, dU)) return rc;
     double res[sf::SELPAT_MAX_M];
-    if (!rc) rc = trace_run(p, mapped, mi, dL, std::max<int64_t>(rows_l, 1), dU, std::max<int64_t>(rows_u, 1), nullptr, res);
-    if (dL) (void)hipFree(dL);
-    if (dU) (void)hipFree(dU);
-    if (!rc) std::copy(res, res + mi, out);
-    return rc;
+    if (int rc = trace_run(p, mapped, mi, dL, std::max<int64_t>(rows_l, 1), dU, std::max<int64_t>(rows_u, 1), nullptr, res)) return rc;
+    std::copy(res, res + mi, out);
+    return SF_OK;
 }
 
 int entries_entry(sf_chol_plan* p, bool lu, sf_long count, const sf_long* rows, const sf_long* cols, double* out, sf_long* outside) {
@@ -433,7 +418,7 @@ int entries_entry(sf_chol_plan* p, bool lu, sf_long count, const sf_long* rows, 
     HIP_TRY(hipSetDevice(p->device));
     if (int rc = selpat_stage(p)) return rc;
     const int64_t CH = sf::SELPAT_ENT_CHUNK;
-    int64_t* d_rows = (int64_t*)p->d_sp_stage;
+    int64_t* d_rows = (int64_t*)p->d_sp_stage.get();
     int64_t* d_cols = d_rows + CH;
     double* d_val = (double*)(d_cols + CH);
     unsigned long long* d_cnt = (unsigned long long*)(d_val + CH);

@@ -496,7 +496,7 @@ int condest(sf_chol_plan* p, sf_float* anorm, sf_float* ainv_norm_est) {
     const double* d_anorm = nullptr;
     if (int rc = sf_refine_anorm(p, &d_anorm, st)) return rc;      // |A|_1 of the current values (sf_refine.hip)
     if (!p->d_cond) {
-        HIP_TRY(hipMalloc((void**)&p->d_cond, (2 * (size_t)n + 2) * sizeof(double)));
+        if (p->d_cond.alloc(2 * (size_t)n + 2)) return SF_ERR_HIP;
         p->bytes_condest = (2 * (size_t)n + 2) * sizeof(double);
     }
     double* x = p->d_cond;
