@@ -1,13 +1,12 @@
 // Device plan of the supernodal Cholesky / LU numeric factorization: its release, the values and the stream it works on, execution
-// (run_launches, the segments of a distributed top, the hipGraph form), validation, the overlapped download, reading the factor
+// (run_launches, the segments of a distributed top, the hipGraph form), validation, reading the factor
 // back and importing one, the pivoting policy and the statistics of a plan.  The plan itself -- the level-by-level sweep, its
 // launch list and task tables, the solve and download schedules, the device resources -- is built in sf_plan_build.hip; the
-// solves and everything else that takes columns through the resident factor live in files of their own (sf_solve.hip,
-// sf_apply.hip and the entry points' files).
+// overlapped download (sf_chol_plan_factorize_to_host) is sf_download.hip; the solves and everything else that takes columns
+// through the resident factor live in files of their own (sf_solve.hip, sf_apply.hip and the entry points' files).
 #include <sparseframe_hip.h>
 
 #include <algorithm>
-#include <time.h>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -104,32 +103,6 @@ int sf_chol_plan_sync(sf_chol_plan* p) {
     return p->last_status;
 }
 
-// overlapped download: record the events of everything that is final once `done` launches have been enqueued and
-// tell the copy workers about them
-static hipError_t dl_publish(sf_chol_plan* p, size_t done) {
-    size_t k = p->dl_next_ev;
-    while (k < p->dl_ev_ready.size() && p->dl_ev_ready[k] <= done) {
-        if (p->dl_lu_direct && p->d_fill && k + 1 < p->fill_first.size()) {
-            sf::launch_lu_fill_u11((const sf::FillTile*)p->d_fill + p->fill_first[k], p->fill_first[k + 1] - p->fill_first[k],
-                                   p->d_Lsx, p->d_Lsx + p->xC, p->stream);
-            const hipError_t ef = hipGetLastError();
-            if (ef != hipSuccess) return ef;
-        }
-        const hipError_t e = hipEventRecord(p->dl_events[k], p->stream);
-        if (e != hipSuccess) return e;
-        ++k;
-    }
-    if (k != p->dl_next_ev) {
-        p->dl_next_ev = k;
-        {
-            std::lock_guard<std::mutex> g(p->dl_mu);
-            p->dl_published = k;
-        }
-        p->dl_cv.notify_all();
-    }
-    return hipSuccess;
-}
-
 // This rank's window [lo, hi) of a launch's `total` divisible items (GEMM launches: stream-K units; k_update_small: tiles); all of
 // them unless the launch is split over a group.  The boundaries are the same doubles on the two ranks they separate, so the windows
 // of a group's members tile [0, total) exactly (checked for every launch of 256^3 / 8 by tests/test_config4_schedules.py).
@@ -144,7 +117,7 @@ static inline void launch_window(const Launch& L, int64_t total, int64_t* lo, in
 static int run_launches(sf_chol_plan* p, size_t l0, size_t l1, bool first, bool last, int sync) {
     if (!p->values_set) return SF_ERR_ARG;
     if (p->dry) return SF_ERR_ARG;        // a schedule-only plan has no device side
-    if (p->ooc_groups > 1 && !p->dl_active) return SF_ERR_ARG;      // an out-of-core plan only exists together with its copy-back
+    if (p->ooc_groups > 1 && !p->dl.active) return SF_ERR_ARG;      // an out-of-core plan only exists together with its copy-back
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t st = p->stream;
     struct EventList {      // profiling events; destroyed on every exit path
@@ -222,15 +195,7 @@ static int run_launches(sf_chol_plan* p, size_t l0, size_t l1, bool first, bool 
             case 1: sf::launch_trsm(p->d_trsm + L.first, L.count, p->d_Lsx, pc.pivinv, st); break;
             case 7: {       // out of core: group L.first takes over buffer L.first & 1
                 const int g = (int)L.first;
-                // ... once every piece of group g - 2 has LEFT the device (its DMA into the pinned ring is complete; the copy workers
-                // count) -- with top mode 2 possibly of a later group, whose top panels' places are taken over here.  Everything those
-                // pieces wait for has been enqueued and published by now.
-                const int upto = p->ooc_wait.empty() ? g - 2 : p->ooc_wait[(size_t)g];
-                for (int w = std::max(0, g - 2); w <= upto && w < g; ++w) {
-                    std::unique_lock<std::mutex> lk(p->dl_mu);
-                    p->dl_cv.wait(lk, [&] { return p->dl_abort || p->dl_group_left[(size_t)w].load() <= 0; });
-                    if (p->dl_abort) return SF_ERR_HIP;
-                }
+                if (int rc = sf_dl_wait_groups(p, g)) return rc;    // ... once the pieces that lie in it have left the device
                 if (g >= 2 && p->ooc_buf > 0) {      // (the first factorization step zeroed everything: groups 0 and 1 find clean buffers)
                     const size_t off = (size_t)(g & 1) * (size_t)p->ooc_buf, nb = (size_t)p->ooc_buf * sizeof(double);
                     HIP_TRY(hipMemsetAsync(p->d_Lsx + off, 0, nb, st));
@@ -267,7 +232,7 @@ static int run_launches(sf_chol_plan* p, size_t l0, size_t l1, bool first, bool 
             }
         }
         if (p->profiling) { kinds.push_back(L.kind); mark(); }
-        if (p->dl_active) HIP_TRY(dl_publish(p, li + 1));
+        if (p->dl.active) HIP_TRY(sf_dl_publish(p, li + 1));
     }
     if (last && !p->capturing) HIP_TRY(hipEventRecord(p->ev1, st));
     HIP_TRY(hipGetLastError());
@@ -554,7 +519,7 @@ int sf_seg_bcast_finish(sf_chol_plan* p, sf_long k) {
     if (rc) return rc;
     // the block column is final on this rank NOW: its copy-back pieces carry "ready = lc + 1"; with launches behind the broadcast
     // run_launches publishes them after the first of those, without any it is done here
-    if (p->dl_active && sg.lc == sg.l1) HIP_TRY(dl_publish(p, sg.lc + 1));
+    if (p->dl.active && sg.lc == sg.l1) HIP_TRY(sf_dl_publish(p, sg.lc + 1));
     return run_launches(p, sg.lc, sg.l1, false, k + 1 == (sf_long)p->segments.size(), 0);
 }
 int sf_seg_early(const sf_chol_plan* p, sf_long k) { return (p && k >= 0 && k < (sf_long)p->segments.size() && p->segments[k].early) ? 1 : 0; }
@@ -614,7 +579,7 @@ static int factorize_graph(sf_chol_plan* p, int sync) {
 }
 
 int sf_chol_plan_factorize(sf_chol_plan* p, int sync) {
-    if (p && !p->dry && p->values_set && p->use_graph && p->nranks == 1 && !p->partial && !p->dl_active && !p->profiling) {
+    if (p && !p->dry && p->values_set && p->use_graph && p->nranks == 1 && !p->partial && !p->dl.active && !p->profiling) {
         const int rc = factorize_graph(p, sync);
         if (rc != SF_ERR_HIP) return rc;
         p->use_graph = false;               // capture is not available here: the eager path from now on
@@ -655,341 +620,6 @@ int sf_chol_plan_validate(sf_chol_plan* p, sf_float* residual, sf_float* x_host)
     *residual = (std::isfinite(h[0]) && std::isfinite(h[2])) ? h[0] / (h[1] * h[2] + h[3]) : std::numeric_limits<double>::quiet_NaN();
     if (x_host) memcpy(x_host, x.data(), p->n * sizeof(double));
     return SF_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Overlapped copy-back.  The reference copies finished blocks back on a second stream while it computes
-// (s_cudaStream_copyback, C:2888-2895).  Here: a few host threads, each with its own HIP stream and two pinned
-// staging slots.  A worker pulls the next piece (pieces are sorted by the launch that finishes them): it
-// waits until the main thread has recorded the piece's event on the compute stream, makes its stream wait for that
-// event, starts the D2H into one slot and, while that DMA runs, copies the previous slot into the caller's buffer.
-// The caller's memory is never pinned or registered: fresh (never touched) pages of a just-malloc'ed Lsx are faulted in
-// by the workers in parallel with the factorization (measured: hipHostRegister of fresh memory is a serial 0.06 s/GiB,
-// 1.7 s for the 128^3 factor; tools/host_xfer_bench.hip).
-// ---------------------------------------------------------------------------------------------------
-} // extern "C"
-
-#include <sys/mman.h>
-#include <unistd.h>
-#include <sched.h>
-#include <cctype>
-
-static void dl_fail(sf_chol_plan* p, int code) {
-    int expect = 0;
-    p->dl_error.compare_exchange_strong(expect, code);
-    {
-        std::lock_guard<std::mutex> g(p->dl_mu);
-        p->dl_abort = true;
-    }
-    p->dl_cv.notify_all();
-}
-
-static double dl_now() {
-    struct timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);
-    return t.tv_sec * 1e3 + t.tv_nsec / 1e6;
-}
-
-// The copy workers move the whole factor (30 GB at 128^3) from the pinned staging ring into the caller's pageable Lsx while the
-// factorization runs: ~55 GB/s of memcpy, which on a two-socket host is cheapest from the socket the device hangs on (the ring
-// lives there).  SF_DL_PIN=1 confines the workers to the CPUs of the device's NUMA node (hipDeviceAttributeHostNumaId or the PCI
-// device's sysfs entry), intersected with the affinity mask the process was given.  OFF by default: measured neutral on the
-// two-socket box of this project (profiles/r02_f_struct_slow_mode.txt, part 3 -- the slow calls seen there had another cause, see
-// the stream priorities in plan_create), and a library should not move its caller's threads around without being asked.
-static void dl_lookup_cpus(sf_chol_plan* p) {
-    p->dl_cpus_known = -1;
-    const char* pin_env = sf_exp_env("SF_DL_PIN");
-    if (!pin_env || atoi(pin_env) == 0) return;
-    int node = -1;
-    if (hipDeviceGetAttribute(&node, hipDeviceAttributeHostNumaId, p->device) != hipSuccess) { (void)hipGetLastError(); node = -1; }
-    if (node < 0) {                                              // older runtimes: the PCI device's own sysfs entry
-        char bdf[32] = {0}, path0[96];
-        if (hipDeviceGetPCIBusId(bdf, (int)sizeof bdf, p->device) == hipSuccess) {
-            for (char* q = bdf; *q; ++q) *q = (char)tolower((unsigned char)*q);
-            snprintf(path0, sizeof path0, "/sys/bus/pci/devices/%s/numa_node", bdf);
-            if (FILE* f0 = fopen(path0, "r")) {
-                if (fscanf(f0, "%d", &node) != 1) node = -1;
-                fclose(f0);
-            }
-        } else (void)hipGetLastError();
-    }
-    if (getenv("SF_TRACE")) fprintf(stderr, "[sparseframe-hip]   device %d hangs on NUMA node %d\n", p->device, node);
-    if (node < 0) return;
-    char path[96];
-    snprintf(path, sizeof path, "/sys/devices/system/node/node%d/cpulist", node);
-    FILE* f = fopen(path, "r");
-    if (!f) return;
-    char buf[4096];
-    const bool got = fgets(buf, sizeof buf, f) != nullptr;
-    fclose(f);
-    if (!got) return;
-    cpu_set_t allowed;
-    CPU_ZERO(&allowed);
-    if (sched_getaffinity(0, sizeof allowed, &allowed) != 0) return;
-    for (char* q = buf; *q;) {                                   // "0-63,128-191"
-        char* e = nullptr;
-        const long a = strtol(q, &e, 10);
-        if (e == q) break;
-        long b = a;
-        if (*e == '-') { q = e + 1; b = strtol(q, &e, 10); if (e == q) break; }
-        for (long c = a; c <= b && c < CPU_SETSIZE; ++c)
-            if (c >= 0 && CPU_ISSET((int)c, &allowed)) p->dl_cpus.push_back((int)c);
-        q = (*e == ',') ? e + 1 : e;
-        if (*e != ',') break;
-    }
-    if (!p->dl_cpus.empty()) p->dl_cpus_known = 1;
-}
-
-static void dl_worker(sf_chol_plan* p, int w) {
-    if (p->dl_cpus_known == 1) {
-        cpu_set_t set;
-        CPU_ZERO(&set);
-        for (int c : p->dl_cpus) CPU_SET(c, &set);
-        (void)sched_setaffinity(0, sizeof set, &set);            // this thread only; a failure leaves it where it was
-    }
-    struct CpuNote { sf_chol_plan* p; int w; ~CpuNote() { p->dl_last_cpu[w] = sched_getcpu(); } } note{p, w};
-    if (hipSetDevice(p->device) != hipSuccess) { dl_fail(p, SF_ERR_HIP); return; }
-    hipStream_t ws = p->dl_streams[w];
-    const size_t np = p->dl_pieces.size();
-    const int64_t DL_SLOT = p->dl_slot;
-    const int W = p->dl_workers;
-    size_t prev = np;
-    int prev_slot = 0, slot = 0;
-    auto drain = [&](size_t k, int sl) -> bool {
-        const DlPiece& pc = p->dl_pieces[k];
-        if (hipEventSynchronize(p->dl_done[w][sl]) != hipSuccess) return false;
-        if (pc.group >= 0 && p->dl_group_left) {        // out of core: this piece has left the device
-            if (p->dl_group_left[(size_t)pc.group].fetch_sub(1) == 1) {
-                { std::lock_guard<std::mutex> g(p->dl_mu); }
-                p->dl_cv.notify_all();
-            }
-        }
-        if (!p->dl_trace.empty()) p->dl_trace[3 * k + 1] = dl_now() - p->dl_t0;
-        const double* ring = p->h_ring + ((int64_t)w * 2 + sl) * DL_SLOT;
-        if (pc.s0 >= 0) {
-            // LU, direct form: ring = [ L run | U^T run ]; column j of the reference panel = L column (nsrow) followed by rows
-            // [nscol, nsrow) of the U^T column
-            const double* rl = ring;
-            const double* ru = ring + pc.dev_count;
-            for (int32_t s = pc.s0; s < pc.s1; ++s) {
-                const int64_t nscol = p->h_Super[s + 1] - p->h_Super[s], nsrow = p->h_Lsip[s + 1] - p->h_Lsip[s];
-                const int64_t nb = nsrow - nscol, lda = nsrow + nb;
-                const int64_t j0 = pc.ld > 0 ? pc.j0 : 0, nc = pc.ld > 0 ? pc.ncols : nscol;
-                double* dst = p->dl_host + p->h_Lsxp[s] + j0 * lda;
-                // 2-D U part (one supernode): nb values per column; whole panels: full columns, the first nscol rows skipped
-                const int64_t ustride = pc.ld > 0 ? nb : nsrow, uskip = pc.ld > 0 ? 0 : nscol;
-                for (int64_t c = 0; c < nc; ++c) {
-                    memcpy(dst + c * lda, rl + c * nsrow, (size_t)nsrow * sizeof(double));
-                    if (nb > 0) memcpy(dst + c * lda + nsrow, ru + c * ustride + uskip, (size_t)nb * sizeof(double));
-                }
-                rl += nc * nsrow;
-                ru += nc * ustride;
-            }
-        } else if (pc.ld > 0) {
-            const int64_t rows = pc.ld - pc.skip;
-            for (int64_t c = 0; c < pc.ncols; ++c) {
-                double* col = p->dl_host + pc.host_off + c * pc.ld;
-                memset(col, 0, (size_t)pc.skip * sizeof(double));
-                memcpy(col + pc.skip, ring + c * rows, (size_t)rows * sizeof(double));
-            }
-        } else {
-            memcpy(p->dl_host + pc.host_off, ring, (size_t)pc.count * sizeof(double));
-        }
-        if (!p->dl_trace.empty()) p->dl_trace[3 * k + 2] = dl_now() - p->dl_t0;
-        return true;
-    };
-    // pieces are pulled from one shared counter, in ready order: streams do not all get the same share of the SDMA
-    // engines (measured: with a static round-robin split one worker of three finished at 570 ms, the others at 940 and
-    // 1070 ms), so the split has to be dynamic
-    (void)W;
-    for (size_t k = p->dl_next_piece.fetch_add(1); k < np; k = p->dl_next_piece.fetch_add(1)) {
-        const DlPiece& pc = p->dl_pieces[k];
-        {
-            std::unique_lock<std::mutex> g(p->dl_mu);
-            if (prev < np && !(p->dl_abort || p->dl_published > (size_t)pc.ev)) {
-                // nothing to fetch yet: finish the piece in hand first (an out-of-core plan's enqueue thread may be waiting for
-                // exactly that piece before it publishes anything further)
-                g.unlock();
-                if (!drain(prev, prev_slot)) { dl_fail(p, SF_ERR_HIP); return; }
-                prev = np;
-                g.lock();
-            }
-            p->dl_cv.wait(g, [&] { return p->dl_abort || p->dl_published > (size_t)pc.ev; });
-            if (p->dl_abort) return;
-        }
-        if (!p->dl_trace.empty()) p->dl_trace[3 * k] = dl_now() - p->dl_t0;
-        double* hslot = p->h_ring + ((int64_t)w * 2 + slot) * DL_SLOT;
-        // The piece's event is waited for on the HOST, by this thread, and the copy is enqueued with nothing in front of it.  A
-        // device-side wait (hipStreamWaitEvent, SF_DL_HOST_WAIT=0) sits in the hardware queue the runtime has put this stream on
-        // and holds up whatever else shares that queue -- another worker's copy of a piece that has long been ready, or a stream
-        // of the caller's (the runtime multiplexes all streams of one priority over 4 hardware queues; plan_create has the story).
-        // While the event is still in the future, the previous piece is copied out of the ring first.
-        bool ok = true;
-        if (p->dl_host_wait) {
-            if (prev < np) {
-                const hipError_t q = hipEventQuery(p->dl_events[pc.ev]);
-                if (q != hipSuccess) {
-                    (void)hipGetLastError();            // hipErrorNotReady is not an error
-                    ok = drain(prev, prev_slot);
-                    prev = np;
-                }
-            }
-            ok = ok && hipEventSynchronize(p->dl_events[pc.ev]) == hipSuccess;
-        } else {
-            ok = hipStreamWaitEvent(ws, p->dl_events[pc.ev], 0) == hipSuccess;
-        }
-        const double* src = p->d_Lsx + pc.dev_off;
-        if (pc.s0 >= 0) {
-            // LU, direct form: the L run as it is; the U^T run as it is (whole supernodes) or rows [nscol, nsrow) of its columns
-            const double* usrc = src + p->xC;
-            ok = ok && hipMemcpyAsync(hslot, src, (size_t)pc.dev_count * sizeof(double), hipMemcpyDeviceToHost, ws) == hipSuccess;
-            if (pc.ld > 0) {
-                const int64_t nscol = p->h_Super[pc.s0 + 1] - p->h_Super[pc.s0], nb = pc.ld - nscol;
-                if (nb > 0)
-                    ok = ok && hipMemcpy2DAsync(hslot + pc.dev_count, (size_t)nb * sizeof(double), usrc + nscol, (size_t)pc.ld * sizeof(double),
-                                                (size_t)nb * sizeof(double), (size_t)pc.ncols, hipMemcpyDeviceToHost, ws) == hipSuccess;
-            } else {
-                ok = ok && hipMemcpyAsync(hslot + pc.dev_count, usrc, (size_t)pc.dev_count * sizeof(double), hipMemcpyDeviceToHost, ws) == hipSuccess;
-            }
-            ok = ok && hipEventRecord(p->dl_done[w][slot], ws) == hipSuccess;
-            if (ok && prev < np) ok = drain(prev, prev_slot);
-            if (!ok) { dl_fail(p, SF_ERR_HIP); return; }
-            prev = k;
-            prev_slot = slot;
-            slot ^= 1;
-            continue;
-        }
-        if (ok && p->lu) {
-            double* dslot = p->d_ring + ((int64_t)w * 2 + slot) * DL_SLOT;
-            sf::launch_pack_lu(p->d_Super, p->d_Lsip, p->d_Xp, p->d_Lsxp, (int32_t)p->nsuper, p->d_Lsx, p->d_Lsx + p->xC,
-                               dslot, pc.host_off, pc.host_off + pc.count, ws);
-            ok = hipGetLastError() == hipSuccess;
-            src = dslot;
-        }
-        if (pc.ld > 0) {
-            const size_t rb = (size_t)(pc.ld - pc.skip) * sizeof(double);
-            ok = ok && hipMemcpy2DAsync(hslot, rb, src + pc.skip, (size_t)pc.ld * sizeof(double), rb, (size_t)pc.ncols, hipMemcpyDeviceToHost, ws) == hipSuccess;
-        } else {
-            ok = ok && hipMemcpyAsync(hslot, src, (size_t)pc.count * sizeof(double), hipMemcpyDeviceToHost, ws) == hipSuccess;
-        }
-        ok = ok && hipEventRecord(p->dl_done[w][slot], ws) == hipSuccess;
-        if (ok && prev < np) ok = drain(prev, prev_slot);
-        if (!ok) { dl_fail(p, SF_ERR_HIP); return; }
-        prev = k;
-        prev_slot = slot;
-        slot ^= 1;
-    }
-    if (prev < np && !drain(prev, prev_slot)) dl_fail(p, SF_ERR_HIP);
-}
-
-int sf_dl_begin(sf_chol_plan* p, double* host_out) {
-    if (!p || !host_out || p->dl_active) return SF_ERR_ARG;
-    if (p->dry) return SF_ERR_ARG;        // a schedule-only plan has no device side
-    HIP_TRY(hipSetDevice(p->device));
-    if (p->dl_cpus_known == 0) dl_lookup_cpus(p);
-    if (!p->h_ring) {
-        const size_t rb = (size_t)std::max(p->dl_workers, p->dl_workers_fresh) * 2 * p->dl_slot * sizeof(double);
-        if (p->h_ring.alloc(rb / sizeof(double))) return SF_ERR_HIP;
-        if (p->lu && !p->dl_lu_direct) {
-            if (p->d_ring.alloc(rb / sizeof(double))) return SF_ERR_HIP;
-            p->bytes_device += rb;
-        }
-        for (int w = 0; w < std::max(p->dl_workers, p->dl_workers_fresh); ++w) {
-            HIP_TRY(hipStreamCreateWithFlags(p->dl_streams[w].put(), hipStreamNonBlocking));
-            for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreateWithFlags(p->dl_done[w][k].put(), hipEventDisableTiming));
-        }
-    }
-    // transparent huge pages for the destination (this box: THP = madvise): 512x fewer first-touch faults when the
-    // caller hands over a just-malloc'ed Lsx, harmless otherwise
-    if (p->xsize > 0) {
-        const uintptr_t pg = (uintptr_t)2 << 20;
-        const uintptr_t a = ((uintptr_t)host_out + pg - 1) & ~(pg - 1), b = ((uintptr_t)(host_out + p->xsize)) & ~(pg - 1);
-        if (b > a) (void)madvise((void*)a, b - a, MADV_HUGEPAGE);
-    }
-    p->dl_host = host_out;
-    p->dl_next_ev = 0;
-    p->dl_next_piece.store(0);
-    if (p->ooc_groups > 1) {
-        if (!p->dl_group_left) p->dl_group_left.reset(new std::atomic<int64_t>[(size_t)p->ooc_groups]);
-        for (int g = 0; g < p->ooc_groups; ++g) p->dl_group_left[(size_t)g].store(p->dl_group_pieces[(size_t)g]);
-    }
-    p->dl_published = 0;
-    p->dl_abort = false;
-    p->dl_error.store(0);
-    p->dl_active = true;
-    p->dl_threads.clear();
-    // SF_DL_TRACE=path: per piece, the times (ms since the start of the download) at which its event was published, its DMA
-    // finished and its copy into the caller's buffer finished
-    p->dl_trace.clear();
-    if (getenv("SF_DL_TRACE")) p->dl_trace.assign(3 * p->dl_pieces.size(), 0.0);
-    p->dl_t0 = dl_now();
-    // A destination whose pages have never been touched (the first call after SparseFrame_analyze malloc'ed Lsx) makes every worker's
-    // memcpy fault its pages in as it goes, and 4 workers no longer keep up with the factorization: 6 bring the first struct call at
-    // 128^3 from 714 to 662 ms; on touched pages 4 are enough and 6 only share hardware queues (sf_plan_internal.h).  mincore() on a
-    // sample of the destination's pages tells the two apart.
-    int nw_call = p->dl_workers;
-    if (p->dl_workers_fresh > nw_call && p->xsize > (int64_t)(64 << 20)) {
-        const long pg = sysconf(_SC_PAGESIZE);
-        int resident = 0, probed = 0;
-        for (int k = 0; k < 16 && pg > 0; ++k) {
-            const uintptr_t a = ((uintptr_t)(host_out + (p->xsize / 16) * k + p->xsize / 32)) & ~((uintptr_t)pg - 1);
-            unsigned char vec = 0;
-            if (mincore((void*)a, (size_t)pg, &vec) == 0) { ++probed; resident += vec & 1; }
-        }
-        if (probed > 0 && 2 * resident < probed) nw_call = p->dl_workers_fresh;
-    }
-    p->dl_workers_last = nw_call;
-    const int nw = (int)std::min<size_t>(nw_call, p->dl_pieces.size());
-    for (int w = 0; w < nw; ++w) p->dl_threads.emplace_back(dl_worker, p, w);
-    // (First touch of a just-malloc'ed destination is left to the copy workers.  Helper threads that populate the page tables ahead
-    // of them -- MADV_POPULATE_WRITE over the array in address order -- were measured and make the first call SLOWER: 637 ms of
-    // copy-back with none, 857 ms with 2, 1100 ms with 8 or 16 at 128^3 (profiles/r03_d_first_call_touch_threads.txt): the page
-    // allocator serialises them with the workers' own faults.)
-    return SF_OK;
-}
-
-int sf_dl_end(sf_chol_plan* p) {
-    if (!p || !p->dl_active) return SF_ERR_ARG;
-    // a factorization that stopped early (an error in the enqueue path) must still release the workers
-    if (p->dl_next_ev < p->dl_ev_ready.size()) {
-        // (everything: an owner-computes block at the very end of the plan is ready "one launch after" its chain, see plan_create)
-        if (hipSetDevice(p->device) != hipSuccess || dl_publish(p, (size_t)-1) != hipSuccess) dl_fail(p, SF_ERR_HIP);
-        if (p->dl_next_ev < p->dl_ev_ready.size()) dl_fail(p, SF_ERR_HIP);
-    }
-    for (std::thread& t : p->dl_threads) t.join();
-    p->dl_threads.clear();
-    p->dl_active = false;
-    p->dl_host = nullptr;
-    if (!p->dl_trace.empty()) {
-        if (FILE* f = fopen(getenv("SF_DL_TRACE") ? getenv("SF_DL_TRACE") : "/dev/null", "w")) {
-            fprintf(f, "piece,ready_launch,doubles,t_published_ms,t_dma_done_ms,t_copied_ms\n");
-            for (size_t k = 0; k < p->dl_pieces.size(); ++k)
-                fprintf(f, "%zu,%zu,%lld,%.3f,%.3f,%.3f\n", k, p->dl_pieces[k].ready, (long long)p->dl_pieces[k].count,
-                        p->dl_trace[3 * k], p->dl_trace[3 * k + 1], p->dl_trace[3 * k + 2]);
-            fclose(f);
-        }
-    }
-    return p->dl_error.load();
-}
-
-extern "C" {
-
-// values H2D + numeric factorization + factor D2H into `host_out` (reference layout, xsize doubles), the download
-// overlapped with the computation.  What one SparseFrame_factorize call does once its plan exists.
-int sf_chol_plan_factorize_to_host(sf_chol_plan* p, const sf_float* Lx, const sf_float* Ux, sf_float* host_out) {
-    if (!p || (!host_out && p->xsize > 0) || p->nranks > 1) return SF_ERR_ARG;
-    struct timespec t0, t1;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    int rc = p->lu ? sf_lu_plan_set_values(p, Lx, Ux) : sf_chol_plan_set_values(p, Lx);
-    if (rc) return rc;
-    if (p->xsize <= 0) return sf_chol_plan_factorize(p, 1);
-    if ((rc = sf_dl_begin(p, host_out))) return rc;
-    rc = sf_chol_plan_factorize(p, 0);
-    const int rc_dl = sf_dl_end(p);
-    const int rc_sync = sf_chol_plan_sync(p);
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    p->last_to_host_ms = (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) / 1e6;
-    return rc ? rc : (rc_sync ? rc_sync : rc_dl);
 }
 
 int sf_chol_plan_top_region(sf_chol_plan* p, void** dptr, sf_long* count) {
@@ -1166,7 +796,7 @@ double sf_chol_plan_stat(const sf_chol_plan* p, const char* name) {
     if (k == "perturbed_pivots") return (double)p->last_perturbed;
     if (k == "pivot_tol") return p->piv_tol;
     if (k == "last_to_host_ms") return p->last_to_host_ms;
-    if (k == "download_pieces") return (double)p->dl_pieces.size();
+    if (k == "download_pieces") return (double)p->dl.pieces.size();
     if (k == "top_doubles") return (double)p->top_size;
     if (k == "stored_doubles") return (double)p->xC;
     if (k == "launches") return (double)p->launches.size();

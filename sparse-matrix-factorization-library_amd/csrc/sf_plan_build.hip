@@ -1130,10 +1130,10 @@ static int kstep_prefixes(PlanTables& T, sf_chol_plan& p) {
 // one staging slot, larger runs cut into slot-sized pieces.  Top panels of a sharded plan are identical on every
 // rank once factored: their pieces are dealt out over the ranks so that every PCIe link carries a share.
 static void schedule_download(const PlanInput& in, const PlanKnobs& kn, const Layout& lay, PlanTables& T, sf_chol_plan& p) {
-    p.dl_workers = kn.dl_workers; p.dl_workers_fresh = kn.dl_workers_fresh;
-    p.dl_host_wait = kn.dl_host_wait;
-    p.dl_slot = kn.dl_slot;
-    const int64_t DL_SLOT = p.dl_slot;
+    p.dl.workers = kn.dl_workers; p.dl.workers_fresh = kn.dl_workers_fresh;
+    p.dl.host_wait = kn.dl_host_wait;
+    p.dl.slot = kn.dl_slot;
+    const int64_t DL_SLOT = p.dl.slot;
     const bool dl_2d = kn.dl_2d;
     std::vector<DlPiece> runs;
     std::vector<uint32_t> run_mask;
@@ -1150,7 +1150,7 @@ static void schedule_download(const PlanInput& in, const PlanKnobs& kn, const La
     bool lu_direct = in.lu && !kn.dl_lu_pack;
     for (sf_long s = 0; s < in.nsuper && lu_direct; ++s)
         if (lay.XP[s] >= 0 && 2 * in.nsrow(s) - in.nscol(s) > DL_SLOT) lu_direct = false;
-    p.dl_lu_direct = lu_direct;
+    p.dl.lu_direct = lu_direct;
     for (sf_long s = 0; s < in.nsuper; ++s) {
         if (lay.XP[s] < 0) continue;
         const int64_t nscol = in.nscol(s), nsrow = in.nsrow(s);
@@ -1229,14 +1229,14 @@ static void schedule_download(const PlanInput& in, const PlanKnobs& kn, const La
             if ((int)(seq % __builtin_popcount(m)) != lay.group_idx(m)) continue;
         }
         if (r.s0 >= 0) {        // LU, direct form
-            if (r.ld == 0) { p.dl_pieces.push_back(r); p.dl_pieces.back().ev = 0; continue; }
+            if (r.ld == 0) { p.dl.pieces.push_back(r); p.dl.pieces.back().ev = 0; continue; }
             const int64_t hld = 2 * r.ld - in.nscol(r.s0), cper = std::max<int64_t>(1, DL_SLOT / hld);
             for (int64_t c = 0; c < r.ncols; c += cper) {
                 DlPiece q = r;
                 q.ev = 0;
                 q.j0 = r.j0 + c; q.ncols = std::min(cper, r.ncols - c);
                 q.dev_off = r.dev_off + c * r.ld; q.host_off = r.host_off + c * hld; q.count = q.ncols * hld; q.dev_count = q.ncols * r.ld;
-                p.dl_pieces.push_back(q);
+                p.dl.pieces.push_back(q);
             }
             continue;
         }
@@ -1244,47 +1244,47 @@ static void schedule_download(const PlanInput& in, const PlanKnobs& kn, const La
             const int64_t rows = r.ld - r.skip, cper = std::max<int64_t>(1, DL_SLOT / std::max<int64_t>(rows, 1));
             if (rows > DL_SLOT) {       // one column longer than a slot (never with the default 32 MiB slot): plain pieces
                 for (int64_t o = 0; o < r.ncols * r.ld; o += DL_SLOT)
-                    p.dl_pieces.push_back(DlPiece{r.dev_off + o, r.host_off + o, std::min(DL_SLOT, r.ncols * r.ld - o), r.ready, 0});
+                    p.dl.pieces.push_back(DlPiece{r.dev_off + o, r.host_off + o, std::min(DL_SLOT, r.ncols * r.ld - o), r.ready, 0});
                 continue;
             }
             for (int64_t c = 0; c < r.ncols; c += cper) {
                 DlPiece q{r.dev_off + c * r.ld, r.host_off + c * r.ld, std::min(cper, r.ncols - c) * rows, r.ready, 0};
                 q.skip = r.skip; q.ld = r.ld; q.ncols = std::min(cper, r.ncols - c);
-                p.dl_pieces.push_back(q);
+                p.dl.pieces.push_back(q);
             }
             continue;
         }
         for (int64_t o = 0; o < r.count; o += DL_SLOT)
-            p.dl_pieces.push_back(DlPiece{r.dev_off + o, r.host_off + o, std::min(DL_SLOT, r.count - o), r.ready, 0});
+            p.dl.pieces.push_back(DlPiece{r.dev_off + o, r.host_off + o, std::min(DL_SLOT, r.count - o), r.ready, 0});
     }
-    std::stable_sort(p.dl_pieces.begin(), p.dl_pieces.end(), [](const DlPiece& a, const DlPiece& b) { return a.ready < b.ready; });
+    std::stable_sort(p.dl.pieces.begin(), p.dl.pieces.end(), [](const DlPiece& a, const DlPiece& b) { return a.ready < b.ready; });
     if (in.ooc()) {
         // the group of every piece (from the supernode its first host entry belongs to) and the number of pieces per group: what
         // the launch that re-uses a buffer waits for
-        p.dl_group_pieces.assign((size_t)in.ooc_ngroups, 0);
-        for (DlPiece& pc : p.dl_pieces) {
+        p.dl.group_pieces.assign((size_t)in.ooc_ngroups, 0);
+        for (DlPiece& pc : p.dl.pieces) {
             const sf_long s = (sf_long)(std::upper_bound(in.Lsxp, in.Lsxp + in.nsuper + 1, (sf_long)pc.host_off) - in.Lsxp) - 1;
             pc.group = (s >= 0 && s < in.nsuper) ? (in.ooc_group[s] >= 0 ? in.ooc_group[s] : (in.ooc_top_mode >= 1 ? p.ooc_last[(size_t)s] : -1)) : -1;
-            if (pc.group >= 0) ++p.dl_group_pieces[(size_t)pc.group];
+            if (pc.group >= 0) ++p.dl.group_pieces[(size_t)pc.group];
         }
     }
-    for (DlPiece& pc : p.dl_pieces) {
-        if (p.dl_ev_ready.empty() || p.dl_ev_ready.back() != pc.ready) p.dl_ev_ready.push_back(pc.ready);
-        pc.ev = (int)p.dl_ev_ready.size() - 1;
+    for (DlPiece& pc : p.dl.pieces) {
+        if (p.dl.ev_ready.empty() || p.dl.ev_ready.back() != pc.ready) p.dl.ev_ready.push_back(pc.ready);
+        pc.ev = (int)p.dl.ev_ready.size() - 1;
     }
     if (lu_direct) {            // the U11 fill tiles of every piece, grouped by the piece's event
-        std::vector<std::vector<sf::FillTile>> by_ev(p.dl_ev_ready.size());
-        for (const DlPiece& pc : p.dl_pieces)
+        std::vector<std::vector<sf::FillTile>> by_ev(p.dl.ev_ready.size());
+        for (const DlPiece& pc : p.dl.pieces)
             for (int32_t s = pc.s0; s < pc.s1; ++s) {
                 const int32_t nscol = (int32_t)in.nscol(s), nsrow = (int32_t)in.nsrow(s);
                 const int32_t cb = pc.ld > 0 ? (int32_t)pc.j0 : 0, ce = pc.ld > 0 ? (int32_t)(pc.j0 + pc.ncols) : nscol;
                 for (int32_t c0 = cb / 64 * 64; c0 < ce; c0 += 64)
                     for (int32_t r0 = 0; r0 <= c0; r0 += 64) by_ev[pc.ev].push_back(sf::FillTile{lay.XP[s], nsrow, r0, c0, cb, ce});
             }
-        p.fill_first.assign(1, 0);
+        p.dl.fill_first.assign(1, 0);
         for (const auto& v : by_ev) {
             T.fill_tiles.insert(T.fill_tiles.end(), v.begin(), v.end());
-            p.fill_first.push_back((int64_t)T.fill_tiles.size());
+            p.dl.fill_first.push_back((int64_t)T.fill_tiles.size());
         }
     }
 }
@@ -1332,7 +1332,7 @@ static int create_device_resources(const PlanInput& in, const PlanKnobs& kn, con
     if (!in.dry && (!new_stream(p.stream, hipStreamDefault) || hipEventCreate(p.ev0.put()) != hipSuccess ||
         hipEventCreate(p.ev1.put()) != hipSuccess || hipEventCreate(p.ev_s0.put()) != hipSuccess ||
         hipEventCreate(p.ev_s1.put()) != hipSuccess)) return SF_ERR_HIP;
-    p.dl_events = std::vector<sf::Event>(p.dl_ev_ready.size());
+    p.dl_events = std::vector<sf::Event>(p.dl.ev_ready.size());
     if (!in.dry) {
         bool ok = true;
         for (sf::Event& e : p.dl_events) ok = ok && hipEventCreateWithFlags(e.put(), hipEventDisableTiming | hipEventBlockingSync) == hipSuccess;    // the copy workers sleep on them
@@ -1400,8 +1400,8 @@ static int create_device_resources(const PlanInput& in, const PlanKnobs& kn, con
     }
     if (!T.fill_tiles.empty()) {
         const size_t fb = T.fill_tiles.size() * sizeof(sf::FillTile);
-        if (!dalloc(p.d_fill, fb)) return SF_ERR_ALLOC;
-        if (!in.dry && hipMemcpy(p.d_fill, T.fill_tiles.data(), fb, hipMemcpyHostToDevice) != hipSuccess) return SF_ERR_HIP;
+        if (!dalloc(p.dl.d_fill, fb)) return SF_ERR_ALLOC;
+        if (!in.dry && hipMemcpy(p.dl.d_fill, T.fill_tiles.data(), fb, hipMemcpyHostToDevice) != hipSuccess) return SF_ERR_HIP;
         p.bytes_device += fb;
     }
     if (!p.segments.empty()) {

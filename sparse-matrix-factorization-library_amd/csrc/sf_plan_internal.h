@@ -3,17 +3,14 @@
 #include <sparseframe_hip.h>
 
 #include <algorithm>
-#include <atomic>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
-#include <memory>
-#include <mutex>
 #include <thread>
 #include <utility>
 #include <vector>
 
 #include "sf_device_mem.h"
+#include "sf_download.h"
 #include "sf_kernels.h"
 
 using sf::GemmProb;
@@ -80,34 +77,6 @@ static inline int upload(sf::DevMem<T>& d, const std::vector<T>& h, size_t* byte
     *bytes_total += count * sizeof(T);
     return SF_OK;
 }
-
-// Overlapped copy-back of the factor (sf_chol_plan_factorize_to_host; the reference overlaps the D2H of finished blocks
-// with compute on s_cudaStream_copyback, C:2888-2895).  A piece is a run of finished panel columns that is contiguous in
-// the host layout (and, for Cholesky, in the device layout), at most DL_SLOT doubles; it may be copied once launch
-// `ready` - 1 has completed (event `ev`).  Pieces are sorted by `ready`.
-constexpr int64_t DL_SLOT_DEFAULT = (int64_t)4 << 20;   // doubles per staging slot (32 MiB)
-constexpr int DL_WORKERS_DEFAULT = 4;                   // copy workers: own HIP stream + 2 pinned slots each.  4 = the number of hardware
-                                                        // queues the runtime gives the ordinary-priority streams: with 6 two pairs of
-                                                        // workers share a queue and the struct call at 128^3 takes 553-603 ms instead of
-                                                        // 552-568 (profiles/r02_f_struct_slow_mode.txt, part 5)
-constexpr int DL_WORKERS_FRESH = 6;
-constexpr int DL_WORKERS_MAX = 16;                      // SF_DL_WORKERS / SF_DL_SLOT_MB (read at plan creation) tune both
-struct DlPiece {
-    int64_t dev_off, host_off, count;   // doubles; LU: dev_off unused (the piece is packed from the (L, U^T) panels)
-    size_t ready;
-    int ev;
-    // Cholesky block columns right of the first one: the rows above the block's first column are structurally zero (never written on
-    // the device either), so only rows [skip, ld) of each of the `ncols` columns cross PCIe (count = ncols * (ld - skip), a 2-D
-    // copy) and the host side zero-fills the prefixes.  ld == 0: a plain contiguous piece.
-    int64_t skip = 0, ld = 0, ncols = 0;
-    // LU (direct form, no pack kernel): the piece is the columns [j0, j0 + ncols) of supernode s0 (s1 == s0 + 1, ld = nsrow: the
-    // L part is one contiguous run of the L panel, the U part -- rows [nscol, nsrow) of the same columns of the U^T panel -- a 2-D
-    // copy) or the whole supernodes [s0, s1) (ld == 0: both panels' runs copied as they are, dev_count doubles each); the copy
-    // worker interleaves the columns into the reference layout (L:2514-2517).  s0 < 0: not an LU-direct piece.
-    int32_t s0 = -1, s1 = -1;
-    int64_t j0 = 0, dev_count = 0;
-    int32_t group = -1;     // out-of-core plans: the streamed group the piece belongs to (-1: a top panel)
-};
 
 // struct path's device pool (sf_handlers.hip): the next plan_create of this thread may use `ptr` for its factor
 extern "C" void sf_plan_offer_factor_buffer(double* ptr, size_t bytes);
@@ -206,13 +175,47 @@ struct SfApply {
 };
 // (the loop itself, a template on its two callables int(double* x, sf_long j0, int cw), follows the plan below)
 
+// The overlapped download of a plan (sf_download.hip).  Its HIP handles -- dl_events, dl_streams, dl_done, h_ring,
+// d_ring -- are NOT here: they stay in sf_plan_handles below, where the release order of DESIGN 8l is written; d_fill is device
+// memory and goes with the plan's members, before every handle.
+struct SfDownload {
+    // ---- the schedule (schedule_download, built once) ----
+    std::vector<DlPiece> pieces;
+    std::vector<size_t> ev_ready;               // launch count after which event k is recorded
+    std::vector<int64_t> group_pieces;          // out-of-core plans: pieces per streamed group (what the gate counts down)
+    // LU direct download: before a piece's event is recorded, the upper triangle (with the diagonal) of its columns' part of the
+    // supernode's diagonal block is filled into the L panel from the U^T panel (k_lu_fill_u11), so that the L panel holds the
+    // reference's packed L11 \ U11 and the download needs no gather kernel
+    bool lu_direct = false;
+    sf::DevMem<sf::FillTile> d_fill;            // sf::FillTile[], grouped by download event
+    std::vector<int64_t> fill_first;            // tiles of event k: [fill_first[k], fill_first[k + 1])
+    // ---- the knobs (SF_DL_SLOT_MB, SF_DL_WORKERS, SF_DL_HOST_WAIT; read at plan creation) ----
+    int64_t slot = DL_SLOT_DEFAULT;
+    int workers = DL_WORKERS_DEFAULT;
+    int workers_fresh = DL_WORKERS_FRESH;       // ... when the destination's pages have never been touched (sf_dl_begin)
+    bool host_wait = true;                      // copy workers wait for a piece's event on the host (see dl_worker)
+    // ---- a running download ----
+    sf::DlGate gate;                            // where the enqueue thread and the copy workers meet (sf_download.h)
+    bool active = false;                        // run_launches records the events and publishes them
+    size_t next_ev = 0;                         // enqueue thread only: the first event not yet recorded
+    double* host = nullptr;                     // destination (reference layout)
+    std::vector<std::thread> threads;
+    std::vector<double> trace;                  // SF_DL_TRACE: 3 times per piece
+    double t0 = 0;
+    int cpus_known = 0;                         // 0 not looked up yet, 1 cpus holds the CPUs of the device's NUMA node, -1 none / disabled
+    std::vector<int> cpus;
+    int last_cpu[DL_WORKERS_MAX] = {};          // CPU each copy worker finished its last download on (SF_TRACE)
+    int workers_last = 0;                       // workers of the last download
+};
+
 // What a plan gives back AFTER its device memory, in this order: the graph, the events, stream2, the download's events, streams and
 // rings, the main stream last.  Members go in reverse order of declaration and a base after the members of the class derived
-// from it, so the order is written here once, backwards, and sf_chol_plan needs no list of what it holds.
+// from it, so the order is written here once, backwards, and sf_chol_plan needs no list of what it holds.  The
+// download's handles stay in this list, not in SfDownload: moving them would move their release before the device memory's.
 struct sf_plan_handles {
     sf::Stream stream;                          // ours, or the caller's (own_stream, sf_chol_plan_set_stream)
     sf::DevMem<double> d_ring;                  // LU: device staging of packed pieces, same shape as h_ring
-    sf::PinnedMem h_ring;                       // pinned staging ring: dl_workers x 2 slots of dl_slot doubles
+    sf::PinnedMem h_ring;                       // pinned staging ring: dl.workers x 2 slots of dl.slot doubles
     sf::Event dl_done[DL_WORKERS_MAX][2];
     sf::Stream dl_streams[DL_WORKERS_MAX];
     std::vector<sf::Event> dl_events;
@@ -224,36 +227,8 @@ struct sf_plan_handles {
 
 struct sf_chol_plan : sf_plan_handles {
     ~sf_chol_plan() { if (!dry) (void)hipSetDevice(device); }       // (the owners free on the plan's device)
-    // ---- overlapped download schedule (built once) and the state of a running download ----
-    std::vector<DlPiece> dl_pieces;
-    std::vector<size_t> dl_ev_ready;            // launch count after which event k is recorded
-    bool dl_active = false;                     // run_launches records the events and publishes them
-    size_t dl_next_ev = 0;
-    std::mutex dl_mu;
-    std::condition_variable dl_cv;
-    size_t dl_published = 0;                    // events [0, dl_published) have been recorded (guarded by dl_mu)
-    bool dl_abort = false;
-    int64_t dl_slot = DL_SLOT_DEFAULT;
-    int dl_workers = DL_WORKERS_DEFAULT;
-    int dl_workers_fresh = DL_WORKERS_FRESH;    // ... when the destination's pages have never been touched (sf_dl_begin)
-    int dl_workers_last = 0;                    // workers of the last download
-    // LU direct download: before a piece's event is recorded, the upper triangle (with the diagonal) of its columns' part of the
-    // supernode's diagonal block is filled into the L panel from the U^T panel (k_lu_fill_u11), so that the L panel holds the
-    // reference's packed L11 \ U11 and the download needs no gather kernel
-    bool dl_host_wait = true;                   // copy workers wait for a piece's event on the host (see dl_worker)
-    bool dl_lu_direct = false;
-    sf::DevMem<sf::FillTile> d_fill;                  // sf::FillTile[], grouped by download event
-    std::vector<int64_t> fill_first;            // tiles of event k: [fill_first[k], fill_first[k + 1])
-    int dl_cpus_known = 0;                      // 0 not looked up yet, 1 dl_cpus holds the CPUs of the device's NUMA node, -1 none / disabled
-    std::vector<int> dl_cpus;
-    int dl_last_cpu[DL_WORKERS_MAX] = {};       // CPU each copy worker finished its last download on (SF_TRACE)
+    SfDownload dl;                              // the overlapped download: schedule, knobs, running state (above)
     double last_to_host_ms = 0;                 // wall time of the last sf_chol_plan_factorize_to_host
-    std::vector<std::thread> dl_threads;
-    std::vector<double> dl_trace;               // SF_DL_TRACE: 3 times per piece
-    double dl_t0 = 0;
-    std::atomic<int> dl_error{0};
-    std::atomic<size_t> dl_next_piece{0};
-    double* dl_host = nullptr;                  // destination of the running download (reference layout)
     // LU pivoting (sf_kernels.h, PivotCtl): threshold inside the 64 x 64 diagonal blocks, perturbation = piv_perturb * max|a_ij|
     // Defaults = the reference's behaviour: no pivoting, no perturbation (magma_dgetrf_nopiv, L:2653); opt-in by sf_lu_plan_set_pivoting,
     // SparseFrame_set_pivoting (struct path) or SF_LU_PIVOT_TOL / SF_LU_PERTURB at plan creation
@@ -277,8 +252,6 @@ struct sf_chol_plan : sf_plan_handles {
     bool partial = false;       // some supernodes are absent or the top panels are not loaded here
     int64_t top_off = 0, top_size = 0;   // contiguous region of the top panels inside one panel set
     size_t launch_split = 0;    // launches [0, launch_split) belong to phase 0, the rest to phase 1
-    // out-of-core plan (plan_create, ooc_group): number of streamed groups (0: in core), entries of one of the two group buffers,
-    // pieces per group and how many of them are still on the device during a download
     // SF_GRAPH=1 (sf_chol_plan_factorize): the resident factorization as one hipGraph
     bool use_graph = false, capturing = false;
     int graph_epoch = 0;
@@ -286,6 +259,8 @@ struct sf_chol_plan : sf_plan_handles {
     double graph_tol = 0, graph_eps = 0;
     hipStream_t graph_stream = nullptr;
     bool factor_borrowed = false;       // d_Lsx holds a buffer the creator lent (sf_plan_offer_factor_buffer, DevMem::lend)
+    // out-of-core plan (plan_create, ooc_group): number of streamed groups (0: in core), entries of one of the two group buffers
+    // (the pieces per group, and how many of them are still on the device during a download: dl.group_pieces and the gate)
     int ooc_groups = 0;
     int64_t ooc_buf = 0;
     // top mode 1 (active top panels only): first / last group below every top supernode, and per group the (offset, length) ranges its
@@ -293,8 +268,6 @@ struct sf_chol_plan : sf_plan_handles {
     int ooc_top_mode = 0;
     std::vector<int32_t> ooc_first, ooc_last, ooc_wait;     // ooc_wait[g]: the last group whose copies group g's first launch waits for
     std::vector<std::vector<std::pair<int64_t, int64_t>>> ooc_zero;
-    std::vector<int64_t> dl_group_pieces;
-    std::unique_ptr<std::atomic<int64_t>[]> dl_group_left;
     int rank = 0, nranks = 1;   // distributed top: this rank's share of the split launches
     std::vector<Segment> segments;
     std::vector<uint32_t> all_masks;    // every group of the factorization (all ranks build the same sorted list)
@@ -482,10 +455,15 @@ int sf_apply_chunks(sf_chol_plan* p, const SfApply& a, SfStretch& t, Body&& body
     return sf_apply_chunks(p, a, t, body, [](double*, sf_long, int) { return SF_OK; });
 }
 
-// Overlapped download (sf_chol_plan.hip).  sf_dl_begin starts the copy workers of a factorization whose launches are
-// about to be enqueued with run_launches (which records and publishes the piece events while dl_active is set);
+// Overlapped download (sf_download.hip).  sf_dl_begin starts the copy workers of a factorization whose launches are
+// about to be enqueued with run_launches (which records and publishes the piece events while dl.active is set);
 // sf_dl_end publishes what is left, waits for the workers and returns SF_OK or the first error.
 int sf_dl_begin(sf_chol_plan* p, double* host_out);
+// run_launches' two calls: record the events of everything that is final once `done` launches have been enqueued and tell the
+// copy workers; out of core, before group g takes over its buffer: wait until the pieces of the groups that held it (and, top mode
+// 2, the top panels whose places it takes) have left the device -- SF_ERR_HIP when the download was aborted meanwhile
+hipError_t sf_dl_publish(sf_chol_plan* p, size_t done);
+int sf_dl_wait_groups(sf_chol_plan* p, int g);
 // the constants of sf_selinv_pattern.hip for sf_chol_plan_stat: 0 the column chunk, 1 entries per part, 2 pairs per staging trip, 3 max m
 double sf_selpat_constant(int which);
 // per-supernode fingerprints (k_factor_hash) of the factor the plan holds, in the reference layout's index space; 0 for panels this

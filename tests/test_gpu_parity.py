@@ -561,6 +561,35 @@ def test_factorize_to_host_overlapped_download(oracle):
     plan.close()
 
 
+@pytest.mark.parametrize("kind", ["chol", "lu"])
+def test_factorize_to_host_many_pieces_equals_get_factor(oracle, monkeypatch, kind):
+    """1 MiB staging slots and 6 copy workers: the 24^3 Laplacian (plain and 2-D pieces) and the 20^3 unsymmetric stencil of
+    test_lu.py (LU direct pieces: whole supernodes and column ranges) come back in dozens of pieces, every worker goes round its
+    two slots several times.  Twice on one plan, against factorize + get_factor of the same plan.  (The LU pack form needs an
+    experiment build or a packed column longer than a slot -- a front of over 65,536 rows; test_lu.py has it.)"""
+    monkeypatch.setenv("SF_DL_SLOT_MB", "1")
+    monkeypatch.setenv("SF_DL_WORKERS", "6")
+    if kind == "chol":
+        n, Cp, Ci, Cx = gen.laplacian_lower(24, 24, 24)
+        sym = sf.analyze(n, Cp, Ci, Cx, sf.grid_nd_perm(24, 24, 24), 8 << 30)
+        plan, values, mask = sf.CholPlan(sym, device=0), (sym.Lx,), oracle.lower_mask(sym)
+    else:
+        n, Cp, Ci, Cx = gen.unsymmetric_stencil(20, 20, 20, seed=7)
+        sym = sf.analyze(n, Cp, Ci, Cx, sf.grid_nd_perm(20, 20, 20), sf.REFERENCE_SLOT_1GPU, "lu", False)
+        plan, values, mask = sf.LUPlan(sym), (sym.Lx, sym.Ux), np.ones(sym.xsize, dtype=bool)
+    assert plan.stat("download_pieces") >= 24            # at least twice the 6 x 2 slots (today: 37 and 275 pieces)
+    plan.set_values(*values)
+    plan.factorize()
+    want = plan.get_factor().copy()
+    out = np.empty(sym.xsize)
+    for _ in range(2):
+        out[:] = np.nan
+        got = plan.factorize_to_host(*values, out=out)
+        assert not np.isnan(got[mask]).any()
+        assert rel_err(got, want, mask) <= TOL_FACTOR
+    plan.close()
+
+
 def test_struct_entry_point_reuses_cached_plan(oracle):
     """SparseFrame_factorize twice on one handler list with the same pattern and new values: the second call finds the
     plan in the handler's cache (no rebuild) and still returns the right factor; a third matrix with another pattern
