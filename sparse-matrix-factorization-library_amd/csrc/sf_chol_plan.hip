@@ -180,7 +180,7 @@ static int run_launches(sf_chol_plan* p, size_t l0, size_t l1, bool first, bool 
     if (first) {
         HIP_TRY(hipMemsetAsync(p->d_info, 0, (1 + p->n_tickets) * sizeof(int), st));
         if (p->xC > 0) HIP_TRY(hipMemsetAsync(p->d_Lsx, 0, (p->lu ? 2 : 1) * p->xC * sizeof(double), st));
-        // (out of core: the top panels only; every group assembles its own buffer when its turn comes, launch kind 7)
+        // (out of core: the top panels only; every group assembles its own buffer when its turn comes, LAUNCH_OOC_GROUP)
         assemble(p->ooc_groups > 1 ? p->d_loadmask + (size_t)p->ooc_groups * (size_t)p->nsuper : p->d_loadmask, st);
     }
     mark();
@@ -188,12 +188,12 @@ static int run_launches(sf_chol_plan* p, size_t l0, size_t l1, bool first, bool 
     for (size_t li = l0; li < l1; ++li) {
         const Launch& L = p->launches[li];
         switch (L.kind) {
-            case 0:
+            case LAUNCH_POTRF:
                 if (p->lu) sf::launch_getrf(p->d_potrf + L.first, L.count, p->d_Lsx, p->xC, p->d_info, pc, st);
                 else sf::launch_potrf(p->d_potrf + L.first, L.count, p->d_Lsx, p->d_info, st);
                 break;
-            case 1: sf::launch_trsm(p->d_trsm + L.first, L.count, p->d_Lsx, pc.pivinv, st); break;
-            case 7: {       // out of core: group L.first takes over buffer L.first & 1
+            case LAUNCH_TRSM: sf::launch_trsm(p->d_trsm + L.first, L.count, p->d_Lsx, pc.pivinv, st); break;
+            case LAUNCH_OOC_GROUP: {       // out of core: group L.first takes over buffer L.first & 1
                 const int g = (int)L.first;
                 if (int rc = sf_dl_wait_groups(p, g)) return rc;    // ... once the pieces that lie in it have left the device
                 if (g >= 2 && p->ooc_buf > 0) {      // (the first factorization step zeroed everything: groups 0 and 1 find clean buffers)
@@ -209,24 +209,24 @@ static int run_launches(sf_chol_plan* p, size_t l0, size_t l1, bool first, bool 
                 assemble(p->d_loadmask + (size_t)g * (size_t)p->nsuper, st);
                 break;
             }
-            case 6: {       // k_update_small; a split launch (distributed top): this rank's share of the tiles (the update is a sum)
+            case LAUNCH_UPDATE_SMALL: {       // k_update_small; a split launch (distributed top): this rank's share of the tiles (the update is a sum)
                 int64_t lo, hi;
                 launch_window(L, L.count, &lo, &hi);
                 sf::launch_update_small(p->d_probs, p->d_stasks + L.first + lo, (int)(hi - lo), p->d_Lsx, p->d_relmap, st);
                 break;
             }
-            case 5:
+            case LAUNCH_STEP:
                 sf::launch_step(p->d_steps + L.first, L.count, p->lu ? 1 : 0, p->d_Lsx, p->d_flags, p->epoch, p->d_info, p->d_tinv,
                                 p->d_info + 1 + L.ticket, pc, st);
                 break;
-            case 2:
-            case 3:
-            case 4: {
+            case LAUNCH_GEMM_INNER:
+            case LAUNCH_GEMM_SCATTER:
+            case LAUNCH_GEMM_OUTER: {
                 int64_t w0, w1;
                 launch_window(L, L.units, &w0, &w1);
                 const uint32_t u0 = (uint32_t)w0, u1 = (uint32_t)w1;
                 sf::launch_gemm(p->d_probs, p->d_gtasks + L.first, p->d_ktprefix + L.prefix_first, L.count, u0, u1,
-                                L.kind == 3 ? 1 : 0, p->d_Lsx, p->d_relmap, p->gemm_dynamic ? p->d_info + 1 + L.ticket : nullptr, st,
+                                L.kind == LAUNCH_GEMM_SCATTER ? 1 : 0, p->d_Lsx, p->d_relmap, p->gemm_dynamic ? p->d_info + 1 + L.ticket : nullptr, st,
                                 (L.whole_tiles && !L.split) ? 1 : 0, 0);
                 break;
             }
@@ -249,7 +249,7 @@ static int run_launches(sf_chol_plan* p, size_t l0, size_t l1, bool first, bool 
         if (dump && first) fprintf(dump, "launch,kind,tasks,units,flops,ms\n");
         for (size_t k = 0; k + 1 < evs.size(); ++k) {
             if (!elapsed_ms(&ms, evs[k], evs[k + 1])) continue;
-            if (kinds[k] == 3) p->last_update_ms += ms; else if (kinds[k] != 6) p->last_panel_ms += ms;
+            if (kinds[k] == LAUNCH_GEMM_SCATTER) p->last_update_ms += ms; else if (kinds[k] != LAUNCH_UPDATE_SMALL) p->last_panel_ms += ms;
             p->last_kind_ms[kinds[k]] += ms;
             if (dump) {
                 const Launch& L = p->launches[l0 + k];
@@ -285,7 +285,7 @@ sf_long sf_chol_plan_num_launches(const sf_chol_plan* p) { return p ? (sf_long)p
 int sf_chol_plan_launch_info(const sf_chol_plan* p, sf_long k, sf_long* out) {
     if (!p || !out || k < 0 || k >= (sf_long)p->launches.size()) return SF_ERR_ARG;
     const Launch& L = p->launches[(size_t)k];
-    const bool gemm = L.kind >= 2 && L.kind <= 4;
+    const bool gemm = launch_is_gemm(L.kind);
     const int64_t total = gemm ? (int64_t)L.units : (int64_t)L.count;
     int64_t lo, hi;
     launch_window(L, total, &lo, &hi);
@@ -811,12 +811,12 @@ double sf_chol_plan_stat(const sf_chol_plan* p, const char* name) {
     if (k == "last_load_ms") return p->last_load_ms;
     if (k == "last_panel_ms") return p->last_panel_ms;
     if (k == "last_update_ms") return p->last_update_ms;
-    if (k == "last_potrf_ms") return p->last_kind_ms[0];
-    if (k == "last_trsm_ms") return p->last_kind_ms[1];
-    if (k == "last_inner_gemm_ms") return p->last_kind_ms[2];
-    if (k == "last_outer_gemm_ms") return p->last_kind_ms[4];
-    if (k == "last_step_ms") return p->last_kind_ms[5];
-    if (k == "last_small_update_ms") return p->last_kind_ms[6];
+    if (k == "last_potrf_ms") return p->last_kind_ms[LAUNCH_POTRF];
+    if (k == "last_trsm_ms") return p->last_kind_ms[LAUNCH_TRSM];
+    if (k == "last_inner_gemm_ms") return p->last_kind_ms[LAUNCH_GEMM_INNER];
+    if (k == "last_outer_gemm_ms") return p->last_kind_ms[LAUNCH_GEMM_OUTER];
+    if (k == "last_step_ms") return p->last_kind_ms[LAUNCH_STEP];
+    if (k == "last_small_update_ms") return p->last_kind_ms[LAUNCH_UPDATE_SMALL];
     if (k == "flops_update_small") return p->flops_update_small;
     if (k == "flops_outer_gemm") return p->flops_outer_gemm;
     if (k == "flops_tiles") return p->flops_tiles;

@@ -41,6 +41,24 @@ struct DlPiece {
 
 namespace sf {
 
+// The download's schedule and knobs: what schedule_download (sf_schedule.cpp) builds once per plan.  SfDownload
+// (sf_plan_internal.h) derives from it and adds the fill tiles' device copy and the state of a running download.
+struct DlSchedule {
+    std::vector<DlPiece> pieces;
+    std::vector<size_t> ev_ready;               // launch count after which event k is recorded
+    std::vector<int64_t> group_pieces;          // out-of-core plans: pieces per streamed group (what the gate counts down)
+    // LU direct download: before a piece's event is recorded, the upper triangle (with the diagonal) of its columns' part of the
+    // supernode's diagonal block is filled into the L panel from the U^T panel (k_lu_fill_u11), so that the L panel holds the
+    // reference's packed L11 \ U11 and the download needs no gather kernel
+    bool lu_direct = false;
+    std::vector<int64_t> fill_first;            // tiles of event k: [fill_first[k], fill_first[k + 1])
+    // ---- the knobs (SF_DL_SLOT_MB, SF_DL_WORKERS, SF_DL_HOST_WAIT; read at plan creation) ----
+    int64_t slot = DL_SLOT_DEFAULT;
+    int workers = DL_WORKERS_DEFAULT;
+    int workers_fresh = DL_WORKERS_FRESH;       // ... when the destination's pages have never been touched (sf_dl_begin)
+    bool host_wait = true;                      // copy workers wait for a piece's event on the host (see dl_worker)
+};
+
 // The one meeting point of a download's threads: the thread that enqueues the factorization (it records the pieces' events and
 // publishes them; in an out-of-core plan it also waits until a group's pieces have left the device before it re-uses the group's
 // buffer) and the copy workers (they claim pieces, wait for a piece's event to be published, and count pieces off their groups).

@@ -12,52 +12,7 @@
 #include "sf_device_mem.h"
 #include "sf_download.h"
 #include "sf_kernels.h"
-
-using sf::GemmProb;
-using sf::GemmTask;
-using sf::PotrfTask;
-using sf::TrsmTask;
-using sf::StepTask;
-
-struct Launch {
-    int kind;       // 0 potrf, 1 trsm, 2 gemm panel (inner, K = NB), 3 gemm scatter, 4 gemm panel (outer, large K),
-                    // 6 Schur updates with K <= SU_MAXK (k_update_small, tasks in stasks),
-                    // 5 fused step k_step (Cholesky, steps of at most GEMM_GRID workgroups; otherwise and for LU: 2, 0, 1)
-    int64_t first;  // first task
-    int count;
-    int64_t prefix_first = 0;   // GEMM launches: first entry of this launch's K-step prefix (count + 1 entries)
-    uint32_t units = 0;         // GEMM launches: total number of (tile, K step) units
-    double flops = 0;           // GEMM launches: algorithmic flops of the problems in this launch
-    bool split = false;         // distributed top: this rank executes the units [share_lo, share_hi) x units of this launch
-    int share_idx = 0, share_cnt = 1;
-    bool whole_tiles = false;   // GEMM launch executed in full by every rank of a group: no K-splitting, bit-identical results (see k_gemm)
-    double share_lo = 0.0, share_hi = 1.0;      // = share_idx / share_cnt, (share_idx + 1) / share_cnt unless the set's shares are weighted
-    int ticket = 0;             // k_step launches: index of the launch's task-claim counter (d_info[1 + ticket])
-};
-
-// Distributed top phase (sf_chol_plan_create_distributed): phase 1 is cut into segments.  Before a segment runs, the
-// regions it lists (the 512-column block of every top panel of the level whose 64-column chain is about to start) are
-// summed over the ranks; until then a block only ever received additive updates (subtree Schur updates, split top
-// Schur updates, split outer GEMMs), so its true value is the sum of the ranks' copies.
-struct Segment {
-    uint32_t mask = 0;                     // the ranks that hold (and sum) these block columns
-    size_t l0 = 0, l1 = 0;                 // launches [l0, l1)
-    std::vector<int64_t> off, cnt;         // whole block columns: doubles, relative to the factor base pointer
-    // the part of each region that can be non-zero (rows >= the block's first column): `cols` pieces of `rows` doubles,
-    // `ld` apart, starting at `src` -- what sf_chol_plan_segment_pack gathers into one contiguous buffer
-    std::vector<int64_t> src, rows, cols, ld;
-    int64_t packed = 0;                    // doubles in the packed buffer
-    // look-ahead schedule: every additive contribution to these block columns except the one of the block column just before
-    // them (which the segment's own first launch adds, replicated) is enqueued before the PREVIOUS segment starts, so the sum
-    // over the ranks may run beside the previous segment's chain
-    bool early = false;
-    // OWNER-COMPUTES prototype (SF_TOP_OWNER=1): the near GEMM and the 64-column chain of this block column,
-    // launches [l0, lc), run on ONE rank of the group only (group index owner_gi = block number mod group size); the finished block
-    // column is then broadcast to the group before the launches [lc, l1) (the split far GEMMs, which read it).  -1: everybody runs
-    // everything (the default: replicate and all-reduce).
-    int owner_gi = -1;
-    size_t lc = 0;
-};
+#include "sf_schedule.h"
 
 #define HIP_TRY(expr)                                                                       \
     do {                                                                                    \
@@ -178,22 +133,8 @@ struct SfApply {
 // The overlapped download of a plan (sf_download.hip).  Its HIP handles -- dl_events, dl_streams, dl_done, h_ring,
 // d_ring -- are NOT here: they stay in sf_plan_handles below, where the release order of DESIGN 8l is written; d_fill is device
 // memory and goes with the plan's members, before every handle.
-struct SfDownload {
-    // ---- the schedule (schedule_download, built once) ----
-    std::vector<DlPiece> pieces;
-    std::vector<size_t> ev_ready;               // launch count after which event k is recorded
-    std::vector<int64_t> group_pieces;          // out-of-core plans: pieces per streamed group (what the gate counts down)
-    // LU direct download: before a piece's event is recorded, the upper triangle (with the diagonal) of its columns' part of the
-    // supernode's diagonal block is filled into the L panel from the U^T panel (k_lu_fill_u11), so that the L panel holds the
-    // reference's packed L11 \ U11 and the download needs no gather kernel
-    bool lu_direct = false;
-    sf::DevMem<sf::FillTile> d_fill;            // sf::FillTile[], grouped by download event
-    std::vector<int64_t> fill_first;            // tiles of event k: [fill_first[k], fill_first[k + 1])
-    // ---- the knobs (SF_DL_SLOT_MB, SF_DL_WORKERS, SF_DL_HOST_WAIT; read at plan creation) ----
-    int64_t slot = DL_SLOT_DEFAULT;
-    int workers = DL_WORKERS_DEFAULT;
-    int workers_fresh = DL_WORKERS_FRESH;       // ... when the destination's pages have never been touched (sf_dl_begin)
-    bool host_wait = true;                      // copy workers wait for a piece's event on the host (see dl_worker)
+struct SfDownload : sf::DlSchedule {             // the schedule and the knobs (schedule_download, built once): sf_download.h
+    sf::DevMem<sf::FillTile> d_fill;            // the LU direct download's sf::FillTile[], grouped by download event (fill_first)
     // ---- a running download ----
     sf::DlGate gate;                            // where the enqueue thread and the copy workers meet (sf_download.h)
     bool active = false;                        // run_launches records the events and publishes them
@@ -225,7 +166,9 @@ struct sf_plan_handles {
     sf::GraphExec graph_exec;
 };
 
-struct sf_chol_plan : sf_plan_handles {
+// The schedule -- every host-only member that plan creation decides from the structure -- is the base SfSchedule (sf_schedule.h);
+// a base goes after the members and sf_plan_handles, declared first, goes last, so the release order above stands.
+struct sf_chol_plan : sf_plan_handles, SfSchedule {
     ~sf_chol_plan() { if (!dry) (void)hipSetDevice(device); }       // (the owners free on the plan's device)
     SfDownload dl;                              // the overlapped download: schedule, knobs, running state (above)
     double last_to_host_ms = 0;                 // wall time of the last sf_chol_plan_factorize_to_host
@@ -236,52 +179,25 @@ struct sf_chol_plan : sf_plan_handles {
     double piv_tol0 = 0.0, piv_perturb0 = 0.0;      // the policy the plan was created with (environment or none): what a struct call without a policy of its own gets
     sf::DevMem<int32_t> d_piv;   // pivpos[n] | pivinv[n] | perturbation counter
     int last_perturbed = 0;
-    bool dry = false;           // schedule-only plan (plan_create's dry mode): no device resources, inspection only
-    bool lu = false;            // no-pivot LU: every supernode has an L panel and a U^T panel (see plan_create)
-    int64_t xC = 0;             // doubles in one set of nsrow x nscol panels (Cholesky: == xsize)
-    int64_t unz = 0;            // LU: entries of U (by row)
     sf::DevMem<int64_t> d_Up;    // LU, unsymmetric input: U by row
     sf::DevMem<int32_t> d_Ui;
     sf::DevMem<double> d_Ux;
     sf::DevMem<int64_t> d_Xp;    // LU: offsets of the nsrow x nscol panels (the reference's Lsxp has the packed sizes)
     sf::DevMem<double> d_pack;   // LU: staging buffer in the reference layout for the download
-    bool u_alias = false;       // LU with a symmetric input: U aliases L (reference L:2718-2729)
-    // multi-GPU sharding: phase[s] = 0 owned subtree supernode, 1 top supernode (replicated), -1 not on this rank
-    std::vector<int8_t> phase;
-    std::vector<int64_t> h_XP;  // device panel offsets (doubles), -1 when the panel is not stored on this rank
-    bool partial = false;       // some supernodes are absent or the top panels are not loaded here
-    int64_t top_off = 0, top_size = 0;   // contiguous region of the top panels inside one panel set
-    size_t launch_split = 0;    // launches [0, launch_split) belong to phase 0, the rest to phase 1
-    // SF_GRAPH=1 (sf_chol_plan_factorize): the resident factorization as one hipGraph
-    bool use_graph = false, capturing = false;
+    // SF_GRAPH=1 (use_graph, sf_chol_plan_factorize): the resident factorization as one hipGraph
+    bool capturing = false;
     int graph_epoch = 0;
-    int32_t n_flags = 1;
     double graph_tol = 0, graph_eps = 0;
     hipStream_t graph_stream = nullptr;
     bool factor_borrowed = false;       // d_Lsx holds a buffer the creator lent (sf_plan_offer_factor_buffer, DevMem::lend)
-    // out-of-core plan (plan_create, ooc_group): number of streamed groups (0: in core), entries of one of the two group buffers
-    // (the pieces per group, and how many of them are still on the device during a download: dl.group_pieces and the gate)
-    int ooc_groups = 0;
-    int64_t ooc_buf = 0;
-    // top mode 1 (active top panels only): first / last group below every top supernode, and per group the (offset, length) ranges its
-    // first launch zeroes for the top panels that start with it
-    int ooc_top_mode = 0;
-    std::vector<int32_t> ooc_first, ooc_last, ooc_wait;     // ooc_wait[g]: the last group whose copies group g's first launch waits for
-    std::vector<std::vector<std::pair<int64_t, int64_t>>> ooc_zero;
-    int rank = 0, nranks = 1;   // distributed top: this rank's share of the split launches
-    std::vector<Segment> segments;
-    std::vector<uint32_t> all_masks;    // every group of the factorization (all ranks build the same sorted list)
     sf::DevMem<double> d_status;    // one word: the ranks' status agreement before the first data collective (sf_multi.hip)
     sf::DevMem<double> d_scratch;   // packed segment buffers (2 x max over the segments: segment k uses half k & 1)
     int64_t scratch_elems = 0;
-    bool top_owner = false;        // SF_TOP_OWNER=1: owner-computes chains for the sets every rank takes part in (prototype, see Segment)
-    bool lookahead = true;         // shared top panels: outer GEMM split into a far part (ahead of the previous chain) and the last block's
     bool unpacked_recorded[2] = {false, false};
     int64_t packed_pending = -1;   // segment whose packed buffer has to be scattered back before it runs
     bool own_stream = true;
     sf::DevMem<int8_t> d_loadmask;
     sf::DevMem<int64_t> d_loadmapL, d_loadmapU;      // whole plans: offset into d_Lsx of every entry of L (/ U), -1 = not loaded
-    std::vector<int64_t> load_dropL, load_dropU;   // entries given again later in their column (the last one is loaded): -1 in the load map
     // device solve (Cholesky, whole matrix on one device): task lists per (level, 64-column step)
     sf::DevMem<sf::SolveTask> d_solve;
     // backward sweep: row-major copies of the diagonal blocks of the top levels' steps (made at the start of every solve)
@@ -290,19 +206,7 @@ struct sf_chol_plan : sf_plan_handles {
     int64_t n_solveT = 0;
     sf::DevMem<double> d_x;
     sf::DevMem<double> d_resid;  // sf_chol_plan_validate: r | column sums | b | 4 norms
-    // the forward launch of a step has fwd_count tasks, the backward one `count` (equal unless the plan is one rank's part of a
-    // distributed factor: the forward tiles that update ancestors' rows are dealt out over the group, the backward ones are not);
-    // big: a panel of the step is wider than 64 columns; red_first / red_count: sums over a group that precede the forward launch
-    struct SolveStep { int64_t fwd_first, bwd_first; int count; int big; int nrows_tasks; int small; int ndiag; int fwd_count; int red_first, red_count; };
-    static constexpr int SOLVE_TICKETS = 3;     // ticket words per step: forward, backward, the backward sweep's second launch (two-launch form)
-    struct SolveReduce { int64_t off, cnt; uint32_t mask; };        // x[off .. off + cnt) summed over the ranks of `mask`
-    std::vector<SolveReduce> solve_reduces;
-    std::vector<std::pair<int64_t, int64_t>> solve_own;           // column ranges whose solution this rank reports (distributed solve)
-    std::vector<std::pair<int64_t, int64_t>> solve_load;          // column ranges whose right-hand side this rank loads
     sf::DevMem<int> d_solve_sync;
-    bool solve_bwd_fused = false;
-    int n_solve_sync = 0;
-    std::vector<SolveStep> solve_steps;
     double last_solve_ms = 0;
     // sf_chol_plan_solve_many: the n x SVM_W row-major block and an n x SVM_W column-major staging buffer for the copies, one
     // allocation made by the first call (not in bytes_device)
@@ -335,8 +239,6 @@ struct sf_chol_plan : sf_plan_handles {
     // ok_gen = that of the last one that succeeded (sf_chol_plan_sync) or of an import; sel_gen = factor_gen the arena was computed from
     int64_t factor_gen = 0, fact_gen = -1, ok_gen = -1, sel_gen = -1;
     bool fact_done = false;         // the last factorization started has had all its launches enqueued
-    std::vector<int32_t> sel_pair_J, sel_pair_i;    // every scatter problem (J, a) as plan_create enumerated it: J, first panel row,
-    std::vector<int64_t> sel_pair_off;              // relative-map offset (host only)
     struct SelBig { sf::SelUnit u; int zslabs, sslabs; };
     struct SelStep { int64_t small_first, small_count, big_first, big_count; };   // one level: big units, then narrow supernodes
     bool sel_scheduled = false;
@@ -380,7 +282,6 @@ struct sf_chol_plan : sf_plan_handles {
     int last_condest_solves = 0;
     double last_condest_ms = 0;
     int device = 0;
-    int64_t n = 0, nsuper = 0, nnz = 0, isize = 0, xsize = 0;
 
     // device copies of the structure
     sf::DevMem<int64_t> d_Lp;
@@ -393,7 +294,6 @@ struct sf_chol_plan : sf_plan_handles {
     sf::DevMem<int64_t> d_Lsxp;
     sf::DevMem<double> d_Lsx;
     sf::DevMem<int> d_info;      // [0]: status bits of the running factorization; [1 ..]: task-claim counters of the k_step launches
-    int n_tickets = 0;
     bool gemm_dynamic = true;   // k_gemm: whole-tile rounds claimed from per-XCD counters (SF_GEMM_DYNAMIC=0: static deal)
 
     sf::DevMem<PotrfTask> d_potrf;
@@ -410,12 +310,6 @@ struct sf_chol_plan : sf_plan_handles {
     sf::DevMem<uint32_t> d_ktprefix;
     sf::DevMem<int32_t> d_relmap;
 
-    std::vector<Launch> launches;
-    int nlevels = 0;
-    int64_t n_gemm_tasks = 0, n_pairs = 0;
-    double flops_tiles = 0, flops_tiles_update = 0;   // MFMA flops the GEMM tiles issue (full 128 x 128 x 16 steps): all launches / Schur updates
-    double flops_update_small = 0;      // part of flops_update done by k_update_small (K <= SU_MAXK)
-    double flops_exec = 0, flops_update = 0, scatter_elems = 0, flops_panel_gemm = 0, flops_outer_gemm = 0;
     size_t bytes_device = 0;
     bool values_set = false;
 
@@ -424,10 +318,6 @@ struct sf_chol_plan : sf_plan_handles {
     double last_kind_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int last_status = SF_OK;
 
-    // host copies needed by the device solve
-    std::vector<int64_t> h_Lsip, h_Lsxp;
-    std::vector<int32_t> h_Super;
-    std::vector<int> level_of;
 };
 
 template <class Body, class Tail>

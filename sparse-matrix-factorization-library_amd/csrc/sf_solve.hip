@@ -712,8 +712,7 @@ void launch_solve_bwd(const SolveTask* t, int nt, int width, int big, const doub
 // ---------------------------------------------------------------------------------------------------
 SolveSync sf_solve_sync(const sf_chol_plan* p) {
     int* w = p->d_solve_sync;       // [info | n_solve_sync sync words | SOLVE_TICKETS tickets per step]
-    const size_t words = 1 + (size_t)p->n_solve_sync + sf_chol_plan::SOLVE_TICKETS * p->solve_steps.size();
-    return SolveSync{w, w ? w + 1 : nullptr, w ? w + 1 + p->n_solve_sync : nullptr, words * sizeof(int)};
+    return SolveSync{w, w ? w + 1 : nullptr, w ? w + 1 + p->n_solve_sync : nullptr, p->solve_sync_words() * sizeof(int)};
 }
 
 void sf_solve_step_fwd(sf_chol_plan* p, size_t k, const double* base, double* x, int width, const SolveSync& y, hipStream_t st) {
