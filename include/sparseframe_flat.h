@@ -320,6 +320,36 @@ int sf_chol_plan_gram(sf_chol_plan *plan, sf_long k, const sf_float *B, sf_long 
  * must not overlap dB (SF_ERR_ARG).  The block goes straight from dB into the Y store: no staging copy. */
 int sf_chol_plan_gram_device(sf_chol_plan *plan, int flags /* 0 | SF_DEV_PERM_IN */, sf_long k,
                              const sf_float *dB, sf_long ldb, sf_float *dG, sf_long ldg);
+/* ---- rank-k update and downdate of the resident factor: A' = A + sign W W^T without a factorization, for a W that
+ * leaves the pattern of L as it is.  W = k sparse columns (Wp[k + 1], Wi, Wx) in the plan's numbering -- with SF_DEV_PERM_IN in the
+ * caller's, mapped through the ordering of sf_chol_plan_set_ordering --, the rows of a column in any order.  A column is ADMISSIBLE
+ * when, with j0 its smallest row and s0 the supernode of j0, every other row is a column of s0 or one of the rows Lsi lists below
+ * s0: a change of a diagonal entry or of the weight of an existing edge, w = alpha (e_i - e_j), always is.  Only the supernodes on
+ * the paths from the s0 to their roots are rewritten, 64 columns per pair of launches; more than 16 columns run as chunks of 16.
+ * Refused with SF_ERR_ARG and nothing changed: sign not SF_UPDATE / SF_DOWNDATE, k < 0, a row outside [0, n), a row twice in a
+ * column, an unknown flag, SF_DEV_PERM_IN without an ordering, an inadmissible column in any chunk (every column is checked before
+ * the first launch; stat "update_bad_column" names the first), LU, schedule-only, partial, sharded, mapped and out-of-core plans,
+ * a plan whose last started factorization has not succeeded.  k == 0: SF_OK, nothing changed.
+ * On success the updated factor counts as factorized, as an imported one does: solves, logdet, selinv (the arena is invalidated:
+ * "selinv_valid" 0), sample, gram and condest see A'.  The plan's stored VALUES are not touched: residual, refine and validate keep
+ * using what set_values last put there -- for a consistent plan call set_values(A') first, then the update.
+ * A downdate that meets d^2 - w^2 <= 0 (A' is not positive definite, or too close) returns SF_ERR_NOT_POSDEF; the factor is then
+ * half rotated and counts as NOT factorized until the next sf_chol_plan_factorize: everything that needs it refuses (SF_ERR_ARG).
+ * The block of W (n x 16 doubles) is allocated by the first call and kept: stat "bytes_update", not in "bytes_device".  Stats:
+ * "last_updown_ms" (device time of the last call's kernels; "last_update_ms" is the factorization's Schur-update phase),
+ * "update_path_supernodes", "update_path_columns", "update_launches". ---- */
+#define SF_UPDATE    1
+#define SF_DOWNDATE -1
+int sf_chol_plan_update(sf_chol_plan *plan, int sign, sf_long k, const sf_long *Wp, const sf_long *Wi, const sf_float *Wx,
+                        int flags /* 0 | SF_DEV_PERM_IN */);
+/* the same with the values in device memory, aligned with Wi (Wp and Wi stay host arrays); the same kernels, the same bits */
+int sf_chol_plan_update_device(sf_chol_plan *plan, int sign, sf_long k, const sf_long *Wp, const sf_long *Wi /* host */,
+                               const sf_float *dWx /* device */, int flags);
+/* the supernodes an update with this pattern would rewrite, ascending (a topological order); needs no device: schedule-only plans
+ * answer too.  *count = their number, supers (NULL or nsuper entries) receives them; *bad_column (may be NULL) = -1, or the first
+ * inadmissible column, in which case the call returns SF_ERR_ARG as for any other bad argument. */
+int sf_chol_plan_update_path(const sf_chol_plan *plan, sf_long k, const sf_long *Wp, const sf_long *Wi, int flags,
+                             sf_long *count, sf_long *supers /* NULL or nsuper entries */, sf_long *bad_column /* or NULL */);
 /* statistics: "levels","launches","gemm_tasks","update_pairs","flops_exec","flops_update",
  * "scatter_elems","bytes_device","last_ms" (device time of the last factorize, HIP events),
  * "last_update_ms","last_panel_ms","last_load_ms" (only when profiling is on) */

@@ -169,6 +169,13 @@ for _n in ("sf_chol_plan_set_value_map", "sf_lu_plan_set_value_map"):
 for _n in ("sf_chol_plan_set_values_mapped_device", "sf_lu_plan_set_values_mapped_device"):
     getattr(lib, _n).argtypes = [C.c_void_p, C.c_void_p]
     getattr(lib, _n).restype = C.c_int
+# rank-k update / downdate of the resident factor (sf_updown.hip); the device form takes the values' address as an integer
+lib.sf_chol_plan_update.argtypes = [C.c_void_p, C.c_int, C.c_int64, c_long_p, c_long_p, c_double_p, C.c_int]
+lib.sf_chol_plan_update.restype = C.c_int
+lib.sf_chol_plan_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int64, c_long_p, c_long_p, C.c_void_p, C.c_int]
+lib.sf_chol_plan_update_device.restype = C.c_int
+lib.sf_chol_plan_update_path.argtypes = [C.c_void_p, C.c_int64, c_long_p, c_long_p, C.c_int, c_long_p, c_long_p, c_long_p]
+lib.sf_chol_plan_update_path.restype = C.c_int
 lib.sf_chol_plan_stat.argtypes = [C.c_void_p, C.c_char_p]
 lib.sf_chol_plan_stat.restype = C.c_double
 lib.sf_chol_plan_set_profiling.argtypes = [C.c_void_p, C.c_int]

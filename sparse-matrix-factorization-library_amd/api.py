@@ -396,13 +396,52 @@ class _ScheduleMixin:
         return xp[:nsuper]
 
 
-class Schedule(_ScheduleMixin, _ShardedPlanMixin):
+def _sparse_columns(W, n, what):
+    """W as k sparse columns: an (n,) or (n, k) array (each column's non-zeros are its pattern) or a (Wp, Wi, Wx) triple (Wx may
+    be None where only the pattern matters) -> (k, Wp, Wi, Wx), int64 / float64 and contiguous"""
+    # (a triple is three array-likes: a plain list of three numbers is a dense vector for n = 3)
+    if isinstance(W, (tuple, list)) and len(W) == 3 and np.ndim(W[0]) == 1 and np.ndim(W[1]) == 1:
+        Wp, Wi = _i64(W[0]), _i64(W[1])
+        Wx = None if W[2] is None else _f64(W[2])
+        if Wp.ndim != 1 or len(Wp) < 1 or Wi.ndim != 1 or len(Wi) < (int(Wp[-1]) if len(Wp) else 0) or \
+                (Wx is not None and Wx.shape != Wi.shape):
+            raise ValueError(f"{what}: (Wp, Wi, Wx) must be k + 1 offsets and Wp[k] rows and values")
+        return len(Wp) - 1, Wp, Wi, Wx
+    W = np.asarray(W, dtype=np.float64)
+    if W.ndim == 1:
+        W = W.reshape(-1, 1)
+    if W.ndim != 2 or W.shape[0] != n:
+        raise ValueError(f"{what}: W must have shape ({n},) or ({n}, k), got {W.shape}")
+    cols, rows = np.nonzero(W.T)
+    Wp = np.zeros(W.shape[1] + 1, dtype=np.int64)
+    np.add.at(Wp, cols + 1, 1)
+    return W.shape[1], np.cumsum(Wp), _i64(rows), _f64(W[rows, cols])
+
+
+class _UpdatePathMixin:
+    """which supernodes a rank-k update would rewrite (sf_chol_plan_update_path): real and schedule-only Cholesky plans"""
+
+    def update_path(self, W, perm_in=False, return_bad=False):
+        """the supernodes, ascending, that update(W) rewrites.  An inadmissible column (or any other bad argument) raises;
+        return_bad: (path or None, first inadmissible column or -1) instead"""
+        k, Wp, Wi, _ = _sparse_columns(W, self.n, "update_path")
+        count, bad = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+        supers = np.zeros(max(self.nsuper, 1), dtype=np.int64)
+        rc = lib.sf_chol_plan_update_path(self._h, k, _lp(Wp), _lp(Wi), 1 if perm_in else 0, _lp(count), _lp(supers), _lp(bad))
+        if return_bad and (rc == 0 or bad[0] >= 0):
+            return (supers[:int(count[0])].copy() if rc == 0 else None), int(bad[0])
+        check(rc, "sf_chol_plan_update_path")
+        return supers[:int(count[0])].copy()
+
+
+class Schedule(_ScheduleMixin, _ShardedPlanMixin, _UpdatePathMixin):
     """Rank `rank`'s plan of an nranks-way factorization WITHOUT a device (sf_chol_plan_schedule_mapped /
     sf_lu_plan_schedule_mapped): the launch list, segments, storage map and byte counts of the real plan, nothing allocated."""
 
     def __init__(self, sym, owner, rank, nranks, lu=False, ooc_group=None, ooc_ngroups=0, ooc_top_mode=0):
         """ooc_group / ooc_ngroups (owner None): the schedule of an out-of-core plan (sf_chol_plan_schedule_ooc)"""
         h = C.c_void_p()
+        self.n = sym.n
         self._keep = [sym.Super, sym.SuperMap, sym.Lsip, sym.Lsi, sym.Lsxp, sym.Lp, sym.Li]
         if ooc_group is not None:
             grp = np.ascontiguousarray(ooc_group, dtype=np.int32)
@@ -787,7 +826,8 @@ class _SelinvPatternMixin:
         return self.selinv_trace(dA, dAU)
 
 
-class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin, _DeviceIOMixin, _SelinvPatternMixin):
+class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin, _DeviceIOMixin, _SelinvPatternMixin,
+               _UpdatePathMixin):
     """Device-resident supernodal Cholesky (flat ABI).  Raises if no HIP device is present.
     phase/load_top: multi-GPU sharding (sf_chol_plan_create_sharded); default = the whole matrix on one device.
     rank/nranks (with phase): distributed top (sf_chol_plan_create_distributed), run with factorize_phase(0) and then
@@ -826,11 +866,34 @@ class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, 
         self._h = h
         self.xsize = sym.xsize
         self.n = sym.n
+        self.nsuper = sym.nsuper
         self._nnz = int(self._keep[5][-1]) if len(self._keep[5]) else 0        # Lp[n]
 
     def set_values(self, Lx):
         Lx = _f64(Lx)
         check(lib.sf_chol_plan_set_values(self._h, _dp(Lx)), "sf_chol_plan_set_values")
+
+    def update(self, W, downdate=False, perm_in=False):
+        """the resident factor of A becomes that of A + W W^T (downdate: A - W W^T) without a factorization (permuted space;
+        perm_in: W's rows are in the caller's numbering, set_ordering).  W: (n,), (n, k) or (Wp, Wi, Wx); every column must be
+        admissible (see update_path): its rows lie in the row list of the supernode of its smallest row -- a diagonal entry or
+        the weight of an existing edge always is.  The stored VALUES stay: set_values(A') first for a consistent plan.  A
+        downdate that loses positive definiteness raises (SF_ERR_NOT_POSDEF) and leaves the plan unfactorized"""
+        k, Wp, Wi, Wx = _sparse_columns(W, self.n, "update")
+        if Wx is None:
+            raise ValueError("update: the values Wx are missing")
+        check(lib.sf_chol_plan_update(self._h, -1 if downdate else 1, k, _lp(Wp), _lp(Wi), _dp(Wx), 1 if perm_in else 0),
+              "sf_chol_plan_update")
+
+    def update_device(self, Wp, Wi, dWx, downdate=False, perm_in=False):
+        """update((Wp, Wi, Wx)) with the values in a 1-D float64 device tensor aligned with Wi"""
+        Wp, Wi = _i64(Wp), _i64(Wi)
+        T, _, _, one = _dev_tensor(dWx, len(Wi), self.device, "update_device")
+        if not one or Wp.ndim != 1 or len(Wp) < 1 or int(Wp[-1]) > len(Wi):
+            raise ValueError("update_device: Wp must hold k + 1 offsets into Wi, dWx one value per row of Wi")
+        self._dev_sync()
+        check(lib.sf_chol_plan_update_device(self._h, -1 if downdate else 1, len(Wp) - 1, _lp(Wp), _lp(Wi), T.data_ptr() or None,
+                                             1 if perm_in else 0), "sf_chol_plan_update_device")
 
     def factorize(self, sync=True):
         check(lib.sf_chol_plan_factorize(self._h, 1 if sync else 0), "sf_chol_plan_factorize")

@@ -135,6 +135,7 @@ static int run_launches(sf_chol_plan* p, size_t l0, size_t l1, bool first, bool 
         p->packed_pending = -1;
         p->epoch = (p->epoch == 0x7fffffff) ? 1 : p->epoch + 1;     // flag value of this factorization's fused steps (never 0)
         p->fact_gen = ++p->factor_gen;
+        p->upd_failed = false;
         p->fact_done = false;
         if (p->capturing) {
             // a captured factorization is replayed with the SAME kernel arguments: its flag value is fixed (never seen in the array
@@ -443,6 +444,7 @@ int sf_plan_import_from(sf_chol_plan* dst, sf_chol_plan* const* parts, int npart
     dst->piv_perturb = parts[0]->piv_perturb;
     dst->hash_epoch = -1;           // the factor changed without a factorization of dst's own: cached fingerprints are stale
     dst->ok_gen = ++dst->factor_gen;        // ... and so is a selected inverse; the imported factor counts as factorized
+    dst->upd_failed = false;
     HIP_TRY(hipStreamSynchronize(dst->stream));
     return SF_OK;
 }
@@ -569,6 +571,7 @@ static int factorize_graph(sf_chol_plan* p, int sync) {
     if (!fresh) {
         p->epoch = (p->epoch == 0x7fffffff) ? 1 : p->epoch + 1;
         p->fact_gen = ++p->factor_gen;
+        p->upd_failed = false;
         p->fact_done = true;
     }
     p->packed_pending = -1;
@@ -793,6 +796,12 @@ double sf_chol_plan_stat(const sf_chol_plan* p, const char* name) {
     if (k == "last_condest_solves") return (double)p->last_condest_solves;
     if (k == "last_condest_ms") return p->last_condest_ms;
     if (k == "bytes_condest") return (double)p->bytes_condest;
+    if (k == "last_updown_ms") return p->last_updown_ms;
+    if (k == "update_path_supernodes") return (double)p->upd_path_supers;
+    if (k == "update_path_columns") return (double)p->upd_path_cols;
+    if (k == "update_launches") return (double)p->upd_launches;
+    if (k == "update_bad_column") return (double)p->upd_bad_column;
+    if (k == "bytes_update") return (double)p->bytes_update;
     if (k == "perturbed_pivots") return (double)p->last_perturbed;
     if (k == "pivot_tol") return p->piv_tol;
     if (k == "last_to_host_ms") return p->last_to_host_ms;

@@ -253,4 +253,21 @@ void launch_refine_update(int64_t n, double* x, const double* d, double* best, i
 void launch_residual(const int64_t* Lp, const int32_t* Li, const double* Lx, const int64_t* Up, const int32_t* Ui, const double* Ux,
                      int32_t n, const double* x, double* r, double* colsum, double* b, double* norms, hipStream_t st);
 
+// ---- rank-k update / downdate of the resident Cholesky factor (sf_updown.hip) ----
+// W: the row-major n x UPD_W block of the update's columns (zero outside their pattern); rot: UPD_B x UPD_W pairs (c, s), pair
+// (j, t) at rot[2 (j UPD_W + t)]; kw: the columns in use rounded up to a power of two (1, 2, 4, 8 or 16 -- the columns behind the
+// chunk are zero and rotate nothing); sign: +1 update, -1 downdate.
+constexpr int UPD_W = 16, UPD_B = 64;
+// W[dest[q]] = val[q], q < count
+void launch_updown_scatter(const int64_t* dest, const double* val, int64_t count, double* W, hipStream_t st);
+// One launch of one wave on the b x b (b <= UPD_B) diagonal block D (column-major, leading dimension ld; only its lower triangle is
+// read and written) whose first column is col0: the b kw rotations in (j, t) order, the pairs to rot, zeros to the rows
+// [col0, col0 + b) of W.  A rotation whose radicand is not positive sets *info to 1 and it and every later one -- of this launch and,
+// *info being read first, of every later launch -- is the identity.
+void launch_updown_diag(double* D, int64_t ld, int b, int kw, int sign, double* W, int64_t col0, double* rot, int* info, hipStream_t st);
+// The same rotations, read from rot, on the nrows panel rows below the block: row i of P (column-major, leading dimension ld, b
+// columns) with row rows[i] of W.  rows[] are distinct.
+void launch_updown_rows(double* P, int64_t ld, int b, int64_t nrows, const int32_t* rows, int kw, int sign, double* W, const double* rot,
+                        hipStream_t st);
+
 }  // namespace sf

@@ -277,6 +277,15 @@ struct sf_chol_plan : sf_plan_handles, SfSchedule {
     double last_refine_berr0 = 0, last_refine_berr = 0, last_refine_ms = 0, last_residual_ms = 0;
     // sf_*_plan_condest (sf_solve_t.hip): x | the sign vector | the iteration's scalars, allocated by the first call (not in
     // bytes_device)
+    // sf_chol_plan_update (sf_updown.hip): the row-major n x UPD_W block of W, the rotation pairs of one 64-column block
+    // and the info word, one allocation made by the first call (bytes_update, not in bytes_device).  upd_failed: a downdate left
+    // the factor half rotated -- it counts as not factorized until the next factorization starts or a factor is imported.
+    sf::DevMem<double> d_upd;
+    size_t bytes_update = 0;
+    bool upd_failed = false;
+    bool upd_w_dirty = true;        // the block of W may hold something: zero it before the next chunk (a finished chunk leaves zeros)
+    double last_updown_ms = 0;
+    int64_t upd_path_supers = 0, upd_path_cols = 0, upd_launches = 0, upd_bad_column = -1;
     sf::DevMem<double> d_cond;
     size_t bytes_condest = 0;
     int last_condest_solves = 0;

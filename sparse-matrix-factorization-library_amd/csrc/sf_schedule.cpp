@@ -1229,6 +1229,11 @@ static void finish_schedule(const PlanInput& in, const Layout& lay, PlanTables& 
     p.h_Lsxp.assign(in.Lsxp, in.Lsxp + in.nsuper + 1);
     p.h_Super.resize((size_t)in.nsuper + 1);
     for (sf_long k = 0; k <= in.nsuper; ++k) p.h_Super[(size_t)k] = (int32_t)in.Super[k];
+    if (!in.lu) {       // the row lists, for the update paths (sf_updown_path.cpp)
+        const sf_long isize = in.nsuper > 0 ? in.Lsip[in.nsuper] : 0;
+        p.h_Lsi.resize((size_t)isize);
+        for (sf_long k = 0; k < isize; ++k) p.h_Lsi[(size_t)k] = (int32_t)in.Lsi[k];
+    }
 }
 
 // ---------------- the whole of it ----------------

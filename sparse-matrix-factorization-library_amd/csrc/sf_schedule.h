@@ -257,6 +257,7 @@ struct SfSchedule {
     // host copies of the structure's pointers (the device solve, the download's unpacking)
     std::vector<int64_t> h_Lsip, h_Lsxp;
     std::vector<int32_t> h_Super;
+    std::vector<int32_t> h_Lsi;     // Cholesky plans: the row lists, what sf_chol_plan_update_path walks (sf_updown_path.h)
 };
 
 // One rank's input of a mapped plan (sf_*_plan_create_mapped / _schedule_mapped) from the owner map of sf_subtree_partition:
