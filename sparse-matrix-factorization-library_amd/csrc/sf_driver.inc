@@ -7,7 +7,7 @@
 // lines are printed (PRINT_INFO is on in the reference's parameter.h:8).  Differences: host threads are std::thread (no OpenMP /
 // omp_set_nested), a stage that fails is reported on stderr and the matrix is skipped (the reference ignores every return code),
 // and the return value is the number of matrices that failed.
-// Included by sf_host.cpp and sf_lu_host.cpp: each library has its own struct layout behind the same names.
+// Included by sf_chol_host.cpp and sf_lu_host.cpp: each library has its own struct layout behind the same names.
 
 int SparseFrame_allocate_matrix(struct common_info_struct* common, struct matrix_info_struct** list) {     // C:368-383
     if (!common || !list) return 1;

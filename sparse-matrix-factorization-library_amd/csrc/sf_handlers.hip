@@ -798,23 +798,4 @@ int64_t sf_handlers_perturbed_pivots(const sf_float* Lsx_host) {
     return it == g_perturbed.end() ? -1 : it->second;
 }
 
-int SparseFrame_allocate_gpu(struct common_info_struct* common, struct gpu_info_struct** list) { return sf_handlers_allocate(common, list); }
-int SparseFrame_free_gpu(struct common_info_struct* common, struct gpu_info_struct** list) { return sf_handlers_free(common, list); }
-
-int SparseFrame_factorize_supernodal(struct common_info_struct* common, struct gpu_info_struct* list,
-                                     struct matrix_info_struct* mi) {
-    if (!common || !mi || !mi->Lsx) return SF_ERR_ARG;
-    return sf_handlers_factorize(common, list, 0, mi->serial, mi->nrow, mi->nsuper, mi->Super, mi->SuperMap, mi->Lsip, mi->Lsi,
-                                 mi->Lsxp, mi->Lp, mi->Li, nullptr, nullptr, mi->Lx, nullptr, mi->Lsx, nullptr);
-}
-
-int SparseFrame_factorize(struct common_info_struct* common, struct gpu_info_struct* list, struct matrix_info_struct* mi) {
-    struct timespec a, b;
-    clock_gettime(CLOCK_REALTIME, &a);
-    const int rc = SparseFrame_factorize_supernodal(common, list, mi);
-    clock_gettime(CLOCK_REALTIME, &b);
-    if (mi) mi->factorizeTime = (b.tv_sec - a.tv_sec) + (b.tv_nsec - a.tv_nsec) / 1.0e9;
-    return rc;
-}
-
 }  // extern "C"

@@ -1,12 +1,17 @@
-// Host solve with the factor in the reference layout, on several threads.
+// Host solve with the factor in the reference layout: the reference's scalar sweep, and the same two sweeps on several threads.
 //
-// The reference's solve is a scalar sweep over Lsx on the host (Cholesky C:3036-3139, LU L:3592-3700); sf_host.cpp / sf_lu_host.cpp
-// keep that sweep as it is for small systems.  The struct path normally solves on the factor that is still resident on the device
-// (sf_handlers_solve_resident_sym); it comes here when there is none -- an out-of-core factorization (the factor only
+// The reference's solve is a scalar sweep over Lsx on the host (Cholesky C:3036-3139, LU L:3592-3700); solve_scalar below keeps that
+// sweep as it is for small systems.  The struct path (sf_struct_path.inc) normally solves on the factor that is still resident on the
+// device (sf_handlers_solve_resident_sym); it comes here when there is none -- an out-of-core factorization (the factor only
 // exists on the host, and two sweeps over host memory at a few hundred GB/s beat two trips over PCIe), several handlers without a
-// gather, an evicted plan, an Lsx the caller changed.  At 128^3 the scalar sweep takes 3.8 s for the 30 GB factor; this one is
+// gather, an evicted plan, an Lsx the caller changed.  At 128^3 the scalar sweep takes 3.8 s for the 30 GB factor; solve_parallel is
 // bound by the host's memory bandwidth.
 //
+//   layout     supernode s: nscol = Super[s+1] - Super[s] columns, nsrow = Lsip[s+1] - Lsip[s] rows (indices Lsi + Lsip[s], the
+//              supernode's own columns first), panel P = Lsx + Lsxp[s], column-major.  Cholesky: lda = nsrow, L(r, c) = P[c lda + r].
+//              LU: lda = 2 nsrow - nscol, L (unit diagonal) in the same places, U11 in the upper part of the diagonal block, U12^T
+//              below L21 at row offset nsrow - nscol; PivInv[g] = position of original row g after the interchanges of its 64-column
+//              block (nullptr: none).
 //   subtrees   sf_subtree_partition cuts the supernodal tree into T sets of subtrees + the supernodes above them ("top").  Every
 //              thread sweeps its own subtrees; what they add to rows of top supernodes goes to a private array per thread and is
 //              summed afterwards (forward), and the backward sweep of a subtree only reads rows that are final by then.
@@ -53,6 +58,49 @@ static inline double upper(const double* P, Long lda, Long nsrow, Long nscol, Lo
     return r < nscol ? P[r * lda + c] : P[(nsrow - nscol) + c * lda + r];
 }
 
+// LU: the rows of the 64-column block that starts at column c of supernode s go to their pivot positions before the block's columns
+// are used (the L entries to the left of the block were stored at the rows' original places)
+static inline void interchange(const Long* Super, const Long* PivInv, Long s, Long c, double* x) {
+    if (!PivInv) return;
+    const Long c0 = Super[s] + c, bw = std::min<Long>(64, Super[s + 1] - c0);
+    bool moved = false;
+    for (Long k = 0; k < bw; ++k) moved = moved || PivInv[c0 + k] != c0 + k;
+    if (!moved) return;
+    double tmp[64];
+    for (Long k = 0; k < bw; ++k) tmp[PivInv[c0 + k] - c0] = x[c0 + k];
+    for (Long k = 0; k < bw; ++k) x[c0 + k] = tmp[k];
+}
+
+// The reference's sweeps, one column at a time in place (C:3036-3139; LU: unit-lower forward, then backward with U11 and U12^T,
+// L:3592-3700).  x: b on entry, the solution on return, permuted numbering.
+template <bool LU>
+void solve_scalar(Long nsuper, const Long* Super, const Long* Lsip, const Long* Lsi, const Long* Lsxp, const double* Lsx,
+                  const Long* PivInv, double* x) {
+    for (Long s = 0; s < nsuper; ++s) {
+        const Long nscol = Super[s + 1] - Super[s], nsrow = Lsip[s + 1] - Lsip[s], lda = LU ? 2 * nsrow - nscol : nsrow;
+        const Long* rows = Lsi + Lsip[s];
+        const double* P = Lsx + Lsxp[s];
+        for (Long c = 0; c < nscol; ++c) {
+            if (LU && c % 64 == 0) interchange(Super, PivInv, s, c, x);
+            const double* col = P + c * lda;
+            const double xj = LU ? x[rows[c]] : (x[rows[c]] /= col[c]);
+            for (Long r = c + 1; r < nsrow; ++r) x[rows[r]] -= col[r] * xj;
+        }
+    }
+    for (Long s = nsuper - 1; s >= 0; --s) {
+        const Long nscol = Super[s + 1] - Super[s], nsrow = Lsip[s + 1] - Lsip[s], lda = LU ? 2 * nsrow - nscol : nsrow;
+        const Long* rows = Lsi + Lsip[s];
+        const double* P = Lsx + Lsxp[s];
+        for (Long c = nscol - 1; c >= 0; --c) {
+            const double* below = P + c * lda + (LU ? nsrow - nscol : 0);       // rows [nscol, nsrow): L21's column, LU: U12^T's
+            double acc = x[rows[c]];
+            for (Long r = c + 1; r < nscol; ++r) acc -= (LU ? P[r * lda + c] : P[c * lda + r]) * x[rows[r]];
+            for (Long r = nscol; r < nsrow; ++r) acc -= below[r] * x[rows[r]];
+            x[rows[c]] = acc / P[c * lda + c];
+        }
+    }
+}
+
 // owner[s]: thread of the subtree holding supernode s, -1 = top (sf_subtree_partition).  PivInv: LU row interchanges or nullptr.
 template <bool LU>
 void solve_parallel(Long n, Long nsuper, const Long* Super, const Long* SuperMap, const Long* Lsip, const Long* Lsi, const Long* Lsxp,
@@ -70,18 +118,6 @@ void solve_parallel(Long n, Long nsuper, const Long* Super, const Long* SuperMap
     std::vector<double> part((size_t)T * 64, 0.0);
     double xb[64];
     SpinBarrier bar(T);
-
-    auto interchange = [&](Long s, Long c) {        // LU: the block's rows go to their pivot positions before the block's columns are used
-        if (!LU || !PivInv) return;
-        const Long nscol = Super[s + 1] - Super[s];
-        const Long c0 = Super[s] + c, bw = std::min<Long>(64, nscol - c);
-        bool moved = false;
-        for (Long k = 0; k < bw; ++k) moved = moved || PivInv[c0 + k] != c0 + k;
-        if (!moved) return;
-        double tmp[64];
-        for (Long k = 0; k < bw; ++k) tmp[PivInv[c0 + k] - c0] = x[c0 + k];
-        for (Long k = 0; k < bw; ++k) x[c0 + k] = tmp[k];
-    };
 
     Long max_nsrow = 1;
     for (Long s = 0; s < nsuper; ++s) max_nsrow = std::max(max_nsrow, Lsip[s + 1] - Lsip[s]);
@@ -107,7 +143,7 @@ void solve_parallel(Long n, Long nsuper, const Long* Super, const Long* SuperMap
             const Long nb = nsrow - nscol;
             for (Long r = 0; r < nb; ++r) t[r] = 0.0;
             for (Long c = 0; c < nscol; ++c) {
-                if (c % 64 == 0) interchange(s, c);
+                if (LU && c % 64 == 0) interchange(Super, PivInv, s, c, x);
                 const double* col = P + c * lda;
                 const double xj = LU ? y[c] : (y[c] /= col[c]);
                 for (Long r = c + 1; r < nscol; ++r) y[r] -= col[r] * xj;
@@ -144,7 +180,7 @@ void solve_parallel(Long n, Long nsuper, const Long* Super, const Long* SuperMap
             for (Long c0 = 0; c0 < nscol; c0 += 64) {
                 const Long bw = std::min<Long>(64, nscol - c0), below = c0 + bw;
                 if (tid == 0) {
-                    interchange(s, c0);
+                    if (LU) interchange(Super, PivInv, s, c0, x);
                     for (Long c = c0; c < below; ++c) {
                         const double* col = P + c * lda;
                         const double xj = LU ? x[rows[c]] : (x[rows[c]] /= col[c]);

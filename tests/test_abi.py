@@ -116,15 +116,20 @@ def test_struct_api_host_side(oracle, tmp_path):
     assert mi.c.residual == res
 
 
-def test_matrix_market_drops_explicit_zeros(tmp_path):
+BOTH_LIBRARIES = pytest.mark.parametrize("mi_cls", [sf.MatrixInfo, sf.LUMatrixInfo], ids=["chol", "lu"])
+
+
+@BOTH_LIBRARIES
+def test_matrix_market_drops_explicit_zeros(tmp_path, mi_cls):
     p = tmp_path / "z.mtx"
     p.write_text("%%MatrixMarket matrix coordinate real symmetric\n% comment\n3 3 5\n1 1 2.0\n2 1 0.0\n2 2 3.0\n3 2 -1.0\n3 3 4.0\n")
-    mi = sf.MatrixInfo()
+    mi = mi_cls()
     mi.read(p)
     assert mi.c.nzmax == 4           # reference C:496 skips the explicit zero
     assert list(mi.array("Cp", 4)) == [0, 1, 3, 4]
 
 
+@BOTH_LIBRARIES
 @pytest.mark.parametrize("text,ok,nz", [
     # integer field, entries of the UPPER triangle, blank lines, several comment lines
     ("%%MatrixMarket matrix coordinate integer symmetric\n% a\n%b\n\n3 3 4\n1 1 2\n1 2 -1\n\n2 2 3\n3 3 4\n", True, 4),
@@ -143,12 +148,15 @@ def test_matrix_market_drops_explicit_zeros(tmp_path):
     # index out of range / rectangular: undefined behaviour in the reference, an error here
     ("%%MatrixMarket matrix coordinate real symmetric\n2 2 1\n3 1 1.0\n", False, 0),
     ("%%MatrixMarket matrix coordinate real general\n2 3 1\n1 1 1.0\n", False, 0),
-], ids=["integer-upper-blank", "general", "complex", "no-banner", "short-size-line", "short-entry", "too-many", "out-of-range", "rectangular"])
-def test_matrix_market_reader_edge_cases(tmp_path, text, ok, nz):
-    """SparseFrame_read_matrix against the reference reader's behaviour (C:400-513) on well- and ill-formed files"""
+    # a size line that announces more entries than any machine holds: the entries that are there are read, nothing is reserved for the rest
+    ("%%MatrixMarket matrix coordinate real symmetric\n2 2 4000000000000000000\n1 1 1.0\n", True, 1),
+], ids=["integer-upper-blank", "general", "complex", "no-banner", "short-size-line", "short-entry", "too-many", "out-of-range", "rectangular",
+        "oversize-size-line"])
+def test_matrix_market_reader_edge_cases(tmp_path, text, ok, nz, mi_cls):
+    """SparseFrame_read_matrix of both libraries against the reference reader's behaviour (C:400-513) on well- and ill-formed files"""
     p = tmp_path / "m.mtx"
     p.write_text(text)
-    mi = sf.MatrixInfo()
+    mi = mi_cls()
     if not ok:
         with pytest.raises(sf.SparseFrameError):
             mi.read(p)
@@ -161,7 +169,8 @@ def test_matrix_market_reader_edge_cases(tmp_path, text, ok, nz):
     mi.cleanup()
 
 
-def test_matrix_market_missing_file(tmp_path):
-    mi = sf.MatrixInfo()
+@BOTH_LIBRARIES
+def test_matrix_market_missing_file(tmp_path, mi_cls):
+    mi = mi_cls()
     with pytest.raises(sf.SparseFrameError):
         mi.read(tmp_path / "does_not_exist.mtx")

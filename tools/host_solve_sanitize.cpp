@@ -50,7 +50,7 @@ int main() {
                 if (S.Super[s + 1] - S.Super[s] >= 8) { const Long c0 = S.Super[s]; pivinv[c0 + 1] = c0 + 5; pivinv[c0 + 5] = c0 + 1; }
         std::vector<double> b(n), x1(n);
         for (Long i = 0; i < n; ++i) b[i] = 1.0 + (double)i / (double)n;
-        // scalar reference sweeps (the loops of sf_host.cpp / sf_lu_host.cpp)
+        // scalar reference sweeps, written out here (the library's are sf_host_solve::solve_scalar)
         x1 = b;
         for (Long s = 0; s < ns; ++s) {
             const Long nscol = S.Super[s + 1] - S.Super[s], nsrow = S.Lsip[s + 1] - S.Lsip[s], lda = lu ? 2 * nsrow - nscol : nsrow;
