@@ -350,6 +350,40 @@ int sf_chol_plan_update_device(sf_chol_plan *plan, int sign, sf_long k, const sf
  * inadmissible column, in which case the call returns SF_ERR_ARG as for any other bad argument. */
 int sf_chol_plan_update_path(const sf_chol_plan *plan, sf_long k, const sf_long *Wp, const sf_long *Wi, int flags,
                              sf_long *count, sf_long *supers /* NULL or nsuper entries */, sf_long *bad_column /* or NULL */);
+/* ---- row deletion and row addition on the resident factor: the companions of the update for taking a variable out
+ * of the system and putting one back, the pattern of L unchanged.  `row` (and Ai) are in the plan's numbering, with SF_DEV_PERM_IN
+ * in the caller's.  With j the row, s its supernode:
+ * rowdel: the factor of A becomes that of A', A with row and column j replaced by the identity's.  Row j of L left of the diagonal
+ * and column j below it become 0, L_jj 1, and the trailing factor takes a rank-1 UPDATE with the old column -- only the supernodes
+ * from s (or its parent, for the last column of s) to the root are rotated.
+ * rowadd: the inverse.  Row and column j of the factor must be the identity's -- after rowdel, or because A was factorized that
+ * way --: this is checked on the device before anything is written (stat "rowmod_not_deleted" 1 when not).  (Ai, Ax)[nz] is the new
+ * column of A, the diagonal among its entries, each index once.  An index i < j is ADMISSIBLE when j is in the row list of the
+ * supernode of i or that supernode is s, an index i > j when it is a column of s or a row below s: the pattern of A's own column
+ * and row j always is.  Row j of L comes from a forward solve along the chains of the indices i < j, L_jj and column j from what it
+ * leaves, and the trailing factor takes a rank-1 DOWNDATE with the new column.
+ * Refused with SF_ERR_ARG and nothing changed: what sf_chol_plan_update refuses; rowadd also a row outside [0, n), an index twice,
+ * a missing diagonal, an inadmissible index (stat "rowmod_bad_index" = its position in Ai), a row that is not the identity's.
+ * rowadd whose a_jj - l12^T l12 is not positive returns SF_ERR_NOT_POSDEF and leaves the plan as a failed downdate does.  On
+ * success the state changes as after an update: the factor counts as factorized, the selected inverse is invalid, the stored
+ * VALUES are untouched -- call set_values(A') first.  Stats: "rowmod_row_tasks" (stretches of row j zeroed or checked),
+ * "rowmod_sweep_supernodes", "rowmod_launches" (every launch of the call, the check included); the device time goes to
+ * "last_updown_ms", the rotated path to the update's stats, "update_launches" counting the rotations' launches only.
+ * "rowmod_bad_index" and "rowmod_not_deleted" describe the last call that passed the update's refusals: each such call starts
+ * them at -1 and 0.  The identity check works in the update's block of W, so a rowadd refused for a row that is not the
+ * identity's has allocated that block ("bytes_update") where no earlier call had; every other refusal allocates nothing.
+ * Accuracy: rowadd forms row j one term per sweep column, in the order of the sweep, so its rounding error grows with the number
+ * of columns the sweep crosses where a factorization sums the same terms in blocks (DESIGN 8q has the measured loss).
+ * Out of scope as for the update: LU, schedule-only (except rowmod_path), partial, sharded, mapped and out-of-core plans. ---- */
+int sf_chol_plan_rowdel(sf_chol_plan *plan, sf_long row, int flags /* 0 | SF_DEV_PERM_IN */);
+int sf_chol_plan_rowadd(sf_chol_plan *plan, sf_long row, sf_long nz, const sf_long *Ai, const sf_float *Ax, int flags);
+/* no device needed: what the two calls would touch.  rows_supers / rows_pos: the supernodes p (ascending) that hold row `row`
+ * below their own columns and its position in their row list; sweep: the supernodes of rowadd's forward sweep (nz = 0, Ai = NULL
+ * for rowdel: empty); update: the path of the rank-1 update that follows.  Every list has room for nsuper entries or is NULL, any
+ * count may be NULL; *bad (may be NULL) = -1 or the first index of Ai that is not admissible (SF_ERR_ARG then) */
+int sf_chol_plan_rowmod_path(const sf_chol_plan *plan, sf_long row, sf_long nz, const sf_long *Ai, int flags,
+                             sf_long *nrows, sf_long *rows_supers, sf_long *rows_pos,
+                             sf_long *nsweep, sf_long *sweep, sf_long *nupdate, sf_long *update, sf_long *bad);
 /* statistics: "levels","launches","gemm_tasks","update_pairs","flops_exec","flops_update",
  * "scatter_elems","bytes_device","last_ms" (device time of the last factorize, HIP events),
  * "last_update_ms","last_panel_ms","last_load_ms" (only when profiling is on) */

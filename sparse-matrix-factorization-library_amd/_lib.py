@@ -176,6 +176,13 @@ lib.sf_chol_plan_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int64, c_lon
 lib.sf_chol_plan_update_device.restype = C.c_int
 lib.sf_chol_plan_update_path.argtypes = [C.c_void_p, C.c_int64, c_long_p, c_long_p, C.c_int, c_long_p, c_long_p, c_long_p]
 lib.sf_chol_plan_update_path.restype = C.c_int
+# row deletion / addition on the resident factor (sf_rowmod.hip)
+lib.sf_chol_plan_rowdel.argtypes = [C.c_void_p, C.c_int64, C.c_int]
+lib.sf_chol_plan_rowdel.restype = C.c_int
+lib.sf_chol_plan_rowadd.argtypes = [C.c_void_p, C.c_int64, C.c_int64, c_long_p, c_double_p, C.c_int]
+lib.sf_chol_plan_rowadd.restype = C.c_int
+lib.sf_chol_plan_rowmod_path.argtypes = [C.c_void_p, C.c_int64, C.c_int64, c_long_p, C.c_int] + [c_long_p] * 8
+lib.sf_chol_plan_rowmod_path.restype = C.c_int
 lib.sf_chol_plan_stat.argtypes = [C.c_void_p, C.c_char_p]
 lib.sf_chol_plan_stat.restype = C.c_double
 lib.sf_chol_plan_set_profiling.argtypes = [C.c_void_p, C.c_int]

@@ -433,6 +433,19 @@ class _UpdatePathMixin:
         check(rc, "sf_chol_plan_update_path")
         return supers[:int(count[0])].copy()
 
+    def rowmod_path(self, row, idx=None, perm_in=False):
+        """what rowdel(row) and rowadd(row, idx, ...) touch (sf_chol_plan_rowmod_path): {"rows": [(supernode, position)] of the
+        panels that hold the row below their own columns, "sweep": the supernodes of rowadd's forward sweep (idx None: empty),
+        "update": the path of the rank-1 update that follows}.  An inadmissible index (or any other bad argument) raises"""
+        Ai = _i64([] if idx is None else idx)
+        cnt = np.zeros(3, dtype=np.int64)
+        out = np.zeros((4, max(self.nsuper, 1)), dtype=np.int64)
+        check(lib.sf_chol_plan_rowmod_path(self._h, int(row), len(Ai), _lp(Ai), 1 if perm_in else 0, _lp(cnt[0:]), _lp(out[0]),
+                                           _lp(out[1]), _lp(cnt[1:]), _lp(out[2]), _lp(cnt[2:]), _lp(out[3]), None),
+              "sf_chol_plan_rowmod_path")
+        return {"rows": list(zip(out[0, :cnt[0]].tolist(), out[1, :cnt[0]].tolist())), "sweep": out[2, :cnt[1]].tolist(),
+                "update": out[3, :cnt[2]].tolist()}
+
 
 class Schedule(_ScheduleMixin, _ShardedPlanMixin, _UpdatePathMixin):
     """Rank `rank`'s plan of an nranks-way factorization WITHOUT a device (sf_chol_plan_schedule_mapped /
@@ -884,6 +897,22 @@ class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, 
             raise ValueError("update: the values Wx are missing")
         check(lib.sf_chol_plan_update(self._h, -1 if downdate else 1, k, _lp(Wp), _lp(Wi), _dp(Wx), 1 if perm_in else 0),
               "sf_chol_plan_update")
+
+    def rowdel(self, row, perm_in=False):
+        """row and column `row` of A become the identity's in the resident factor (permuted space, perm_in: the
+        caller's numbering): the variable leaves the system, the pattern stays.  An iterable deletes its rows one after the
+        other.  The stored VALUES stay: set_values(A') first for a consistent plan"""
+        for r in (row if np.ndim(row) else [row]):
+            check(lib.sf_chol_plan_rowdel(self._h, int(r), 1 if perm_in else 0), "sf_chol_plan_rowdel")
+
+    def rowadd(self, row, idx, vals, perm_in=False):
+        """the inverse of rowdel: row and column `row` of the factor, currently the identity's, take the column (idx, vals) of
+        the new A, the diagonal among its entries; every index must be admissible (see rowmod_path) -- the pattern of A's own
+        column always is.  A column that leaves A indefinite raises (SF_ERR_NOT_POSDEF) and leaves the plan unfactorized"""
+        Ai, Ax = _i64(idx), _f64(vals)
+        if Ai.ndim != 1 or Ax.shape != Ai.shape:
+            raise ValueError("rowadd: idx and vals must be 1-D and of one length")
+        check(lib.sf_chol_plan_rowadd(self._h, int(row), len(Ai), _lp(Ai), _dp(Ax), 1 if perm_in else 0), "sf_chol_plan_rowadd")
 
     def update_device(self, Wp, Wi, dWx, downdate=False, perm_in=False):
         """update((Wp, Wi, Wx)) with the values in a 1-D float64 device tensor aligned with Wi"""

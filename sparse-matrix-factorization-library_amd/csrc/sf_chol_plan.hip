@@ -801,6 +801,11 @@ double sf_chol_plan_stat(const sf_chol_plan* p, const char* name) {
     if (k == "update_path_columns") return (double)p->upd_path_cols;
     if (k == "update_launches") return (double)p->upd_launches;
     if (k == "update_bad_column") return (double)p->upd_bad_column;
+    if (k == "rowmod_row_tasks") return (double)p->rowmod_row_tasks;
+    if (k == "rowmod_sweep_supernodes") return (double)p->rowmod_sweep_supers;
+    if (k == "rowmod_launches") return (double)p->rowmod_launches;
+    if (k == "rowmod_bad_index") return (double)p->rowmod_bad_index;
+    if (k == "rowmod_not_deleted") return (double)p->rowmod_not_deleted;
     if (k == "bytes_update") return (double)p->bytes_update;
     if (k == "perturbed_pivots") return (double)p->last_perturbed;
     if (k == "pivot_tol") return p->piv_tol;

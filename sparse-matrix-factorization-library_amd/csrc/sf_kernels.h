@@ -270,4 +270,23 @@ void launch_updown_diag(double* D, int64_t ld, int b, int kw, int sign, double* 
 void launch_updown_rows(double* P, int64_t ld, int b, int64_t nrows, const int32_t* rows, int kw, int sign, double* W, const double* rot,
                         hipStream_t st);
 
+// ---- row deletion / addition on the resident Cholesky factor (sf_rowmod.hip); W, UPD_W, UPD_B as above, column 0 ----
+// One launch over ntasks tasks (tasks[3 q ..]: offset of the first entry from L, stride, length), one workgroup each.  check == 0:
+// the entries <- 0, nothing else is written.  check != 0: nothing of L is written; *flag <- 1 when an entry is not zero or, with
+// one_off >= 0, L[one_off] is not 1 (*flag is never cleared).  ntasks <= 0: no launch.
+void launch_rowmod_zero_rows(double* L, const int64_t* tasks, int64_t ntasks, int64_t one_off, int check, int* flag, hipStream_t st);
+// col = the address of L_jj in its panel, the nbelow entries behind it the column below the diagonal, rows[i] the row of entry
+// 1 + i:  W[rows[i]] <- col[1 + i], col[1 + i] <- 0, col[0] <- 1
+void launch_rowdel_column(double* col, int64_t nbelow, const int32_t* rows, double* W, hipStream_t st);
+// One launch of one wave: D y = W[col0 .. col0 + b) on the b x b block D (lower triangle read only), y to y[0 .. b), zeros to
+// column 0 of those rows of W
+void launch_rowadd_sweep_diag(const double* D, int64_t ld, int b, double* W, int64_t col0, double* y, hipStream_t st);
+// The nrows panel rows below the block: W[rows[i]] -= sum_col P(i, col) y[col], column after column.  The row with rows[i] ==
+// target (-1: none) is first overwritten with y.  rows[] are distinct.
+void launch_rowadd_sweep_rows(double* P, int64_t ld, int b, int64_t nrows, const int32_t* rows, int32_t target, double* W, const double* y,
+                              hipStream_t st);
+// One workgroup.  d = W[jrow]: not positive, NaN, or *info set on entry: *info <- 1 and nothing else is written.  Otherwise
+// col[0] <- sqrt(d), col[1 + i] <- W[rows[i]] / sqrt(d), which also stays in W[rows[i]], and W[jrow] <- 0.
+void launch_rowadd_column(double* col, int64_t nbelow, const int32_t* rows, double* W, int64_t jrow, int* info, hipStream_t st);
+
 }  // namespace sf

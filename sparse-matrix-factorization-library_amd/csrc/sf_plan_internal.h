@@ -13,6 +13,7 @@
 #include "sf_download.h"
 #include "sf_kernels.h"
 #include "sf_schedule.h"
+#include "sf_updown_path.h"
 
 #define HIP_TRY(expr)                                                                       \
     do {                                                                                    \
@@ -77,6 +78,28 @@ void tsolve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, h
 // diagonal copies, made from the L panels)
 void tsolve_sweep_fwd(sf_chol_plan* p, double* x, int width, const SolveSync& y, hipStream_t st);
 void tsolve_sweep_bwd(sf_chol_plan* p, double* x, int width, bool transpose_diag, const SolveSync& y, hipStream_t st);
+// ---- shared by the update / downdate and the row modifications (sf_updown.hip, sf_rowmod.hip) ----
+// the refusals of sf_chol_plan_update that do not depend on W: LU, an unknown flag, a plan that is not whole and resident,
+// SF_DEV_PERM_IN without an ordering, no usable factor.  SF_OK: the plan's device is current.
+int sf_updown_accepts(sf_chol_plan* p, int flags);
+sf::UpdownStruct sf_updown_struct(const sf_chol_plan* p);
+// the inverse of the ordering of sf_chol_plan_set_ordering: iperm[old] = new
+int sf_updown_inverse_ordering(const sf_chol_plan* p, std::vector<int32_t>& iperm);
+// the plan's update block d_upd (allocated by the first call of sf_updown_block): the n x UPD_W block of W, the pairs of one
+// diagonal block, the info word
+struct SfUpdownBlock { double *W, *rot; int* info; };
+int sf_updown_block(sf_chol_plan* p);
+SfUpdownBlock sf_updown_parts(sf_chol_plan* p);
+// zero W on the plan's stream unless the last chunk left it zero; W counts as dirty from here until the caller says otherwise
+int sf_updown_clear_w(sf_chol_plan* p);
+// Rotate the block of W that is already on the device along `supers` (ascending): the pair of launches of every 64-column block,
+// on the plan's stream, nothing waited for.  Returns the number of launches.
+int64_t sf_updown_rotate(sf_chol_plan* p, const std::vector<int64_t>& supers, int sign, int kw);
+// record ev_s1, read the info word, wait for the stream
+int sf_updown_collect(sf_chol_plan* p, int* h_info);
+// the state protocol after the factor was written (rrc: what the launches and sf_updown_collect returned): the stats, hash_epoch,
+// factor_gen, fact_done, ok_gen; a failure (rrc or h_info) leaves upd_failed.  Returns the call's status.
+int sf_updown_commit(sf_chol_plan* p, int rrc, int h_info, const std::vector<int64_t>& supers, int64_t launches);
 // ---- the host protocol of every entry point that takes columns through the resident factor (sf_apply.hip) ----
 // the plan is whole and resident: one rank's, in core, with the solve's task lists
 bool sf_plan_whole_resident(const sf_chol_plan* p);
@@ -286,6 +309,8 @@ struct sf_chol_plan : sf_plan_handles, SfSchedule {
     bool upd_w_dirty = true;        // the block of W may hold something: zero it before the next chunk (a finished chunk leaves zeros)
     double last_updown_ms = 0;
     int64_t upd_path_supers = 0, upd_path_cols = 0, upd_launches = 0, upd_bad_column = -1;
+    // sf_chol_plan_rowdel / _rowadd (sf_rowmod.hip) work in the same block; what the last call did
+    int64_t rowmod_row_tasks = 0, rowmod_sweep_supers = 0, rowmod_launches = 0, rowmod_bad_index = -1, rowmod_not_deleted = 0;
     sf::DevMem<double> d_cond;
     size_t bytes_condest = 0;
     int last_condest_solves = 0;

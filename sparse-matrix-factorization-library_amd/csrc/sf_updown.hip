@@ -167,9 +167,7 @@ void launch_updown_rows(double* P, int64_t ld, int b, int64_t nrows, const int32
 // ---------------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------------
-namespace {
-
-sf::UpdownStruct updown_struct(const sf_chol_plan* p) {
+sf::UpdownStruct sf_updown_struct(const sf_chol_plan* p) {
     sf::UpdownStruct S;
     S.n = p->n;
     S.nsuper = p->nsuper;
@@ -180,7 +178,7 @@ sf::UpdownStruct updown_struct(const sf_chol_plan* p) {
 }
 
 // the inverse of the ordering of sf_chol_plan_set_ordering: iperm[old] = new
-int inverse_ordering(const sf_chol_plan* p, std::vector<int32_t>& iperm) {
+int sf_updown_inverse_ordering(const sf_chol_plan* p, std::vector<int32_t>& iperm) {
     std::vector<int32_t> perm((size_t)std::max<int64_t>(p->n, 1));
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipMemcpy(perm.data(), p->d_perm, (size_t)p->n * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -189,15 +187,30 @@ int inverse_ordering(const sf_chol_plan* p, std::vector<int32_t>& iperm) {
     return SF_OK;
 }
 
+namespace {
+
 int kernel_width(int cw) {
     int kw = 1;
     while (kw < cw) kw *= 2;
     return kw;
 }
 
+}  // namespace
+
+// ---- what the row modifications share with the update (sf_plan_internal.h) ----
+int sf_updown_accepts(sf_chol_plan* p, int flags) {
+    if (!p || p->lu) return SF_ERR_ARG;
+    if (flags & ~SF_DEV_PERM_IN) return SF_ERR_ARG;
+    if (!sf_plan_whole_resident(p)) return SF_ERR_ARG;
+    if ((flags & SF_DEV_PERM_IN) && !p->d_perm) return SF_ERR_ARG;
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->upd_failed || !sf_factor_usable(p)) return SF_ERR_ARG;
+    return SF_OK;
+}
+
 // the block of W, the pairs of one diagonal block, the info word
 constexpr size_t UPD_ROT = 2 * (size_t)sf::UPD_B * sf::UPD_W;
-int updown_block(sf_chol_plan* p) {
+int sf_updown_block(sf_chol_plan* p) {
     if (p->d_upd) return SF_OK;
     const size_t count = (size_t)p->n * sf::UPD_W + UPD_ROT + 1;
     if (int rc = p->d_upd.alloc(count)) return rc;
@@ -205,82 +218,49 @@ int updown_block(sf_chol_plan* p) {
     return SF_OK;
 }
 
-int update_run(sf_chol_plan* p, int sign, sf_long k, const sf_long* Wp, const sf_long* Wi, const sf_float* Wx, bool wx_dev, int flags) {
-    if (!p || p->lu || (sign != SF_UPDATE && sign != SF_DOWNDATE) || k < 0 || !Wp) return SF_ERR_ARG;
-    if (flags & ~SF_DEV_PERM_IN) return SF_ERR_ARG;
-    if (!sf_plan_whole_resident(p)) return SF_ERR_ARG;
-    if ((flags & SF_DEV_PERM_IN) && !p->d_perm) return SF_ERR_ARG;
-    HIP_TRY(hipSetDevice(p->device));
-    if (p->upd_failed || !sf_factor_usable(p)) return SF_ERR_ARG;
-    std::vector<int32_t> iperm;
-    if (flags & SF_DEV_PERM_IN)
-        if (int rc = inverse_ordering(p, iperm)) return rc;
-    std::vector<int64_t> supers;
-    std::vector<int32_t> rows;
-    int64_t bad = -1;
-    const int prc = sf::updown_path(updown_struct(p), k, Wp, Wi, iperm.empty() ? nullptr : iperm.data(), supers, &bad, &rows);
-    if (prc == sf::UPDOWN_INADMISSIBLE) p->upd_bad_column = bad;      // (the stat that names it; nothing else of the plan changes)
-    if (prc != sf::UPDOWN_OK) return SF_ERR_ARG;
-    const int64_t nz = Wp[k] - Wp[0];
-    if (nz > 0 && !Wx) return SF_ERR_ARG;
-    if (wx_dev && nz > 0 && !sf_device_ptr_ok(p, Wx + Wp[0], (size_t)nz)) return SF_ERR_ARG;
-    if (k == 0) return SF_OK;
-    if (int rc = updown_block(p)) return rc;
+SfUpdownBlock sf_updown_parts(sf_chol_plan* p) {
+    SfUpdownBlock B;
+    B.W = p->d_upd;
+    B.rot = B.W + (size_t)p->n * sf::UPD_W;
+    B.info = (int*)(B.rot + UPD_ROT);
+    return B;
+}
 
+int sf_updown_clear_w(sf_chol_plan* p) {
+    if (p->upd_w_dirty) HIP_TRY(hipMemsetAsync(p->d_upd, 0, (size_t)p->n * sf::UPD_W * sizeof(double), p->stream));
+    p->upd_w_dirty = true;
+    return SF_OK;
+}
+
+int64_t sf_updown_rotate(sf_chol_plan* p, const std::vector<int64_t>& supers, int sign, int kw) {
     hipStream_t st = p->stream;
-    double* W = p->d_upd;
-    double* rot = W + (size_t)p->n * sf::UPD_W;
-    int* info = (int*)(rot + UPD_ROT);
-    // where every value goes in the block of its chunk, and the values themselves
-    std::vector<int64_t> dest((size_t)std::max<int64_t>(nz, 1));
-    for (sf_long t = 0; t < k; ++t)
-        for (sf_long q = Wp[t]; q < Wp[t + 1]; ++q) dest[(size_t)(q - Wp[0])] = (int64_t)rows[(size_t)(q - Wp[0])] * sf::UPD_W + t % sf::UPD_W;
-    sf::DevMem<int64_t> d_dest;
-    sf::DevMem<double> d_val;
-    if (int rc = d_dest.alloc(dest.size())) return rc;
-    HIP_TRY(hipMemcpyAsync(d_dest, dest.data(), dest.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    const double* val = Wx ? Wx + Wp[0] : nullptr;
-    if (!wx_dev && nz > 0) {
-        if (int rc = d_val.alloc((size_t)nz)) return rc;
-        HIP_TRY(hipMemcpyAsync(d_val, val, (size_t)nz * sizeof(double), hipMemcpyHostToDevice, st));
-        val = d_val;
-    }
-    HIP_TRY(hipMemsetAsync(info, 0, sizeof(double), st));
-
-    int64_t path_cols = 0, launches = 0;
-    for (int64_t s : supers) path_cols += p->h_Super[s + 1] - p->h_Super[s];
-    int h_info = 0;
-    // From the first launch on the factor may be partly rotated: whatever goes wrong in here, the plan no longer holds a factor.
-    auto rotate = [&]() -> int {
-        HIP_TRY(hipEventRecord(p->ev_s0, st));
-        for (sf_long t0 = 0; t0 < k; t0 += sf::UPD_W) {
-            const int cw = (int)std::min<sf_long>(sf::UPD_W, k - t0), kw = kernel_width(cw);
-            // A finished chunk leaves the block zero again: the diagonal launches zero the rows of their columns, and every row a
-            // row launch writes is a column of an ancestor on the path.  Only a fresh block, or one an error left behind, is cleared.
-            if (p->upd_w_dirty) HIP_TRY(hipMemsetAsync(W, 0, (size_t)p->n * sf::UPD_W * sizeof(double), st));
-            p->upd_w_dirty = true;
-            sf::launch_updown_scatter(d_dest + (Wp[t0] - Wp[0]), val + (Wp[t0] - Wp[0]), Wp[t0 + cw] - Wp[t0], W, st);
-            // (a chunk only touches the chains of its own columns, but a supernode off them sees zero rows of W: identities)
-            for (int64_t s : supers) {
-                const int64_t c0 = p->h_Super[s], nscol = p->h_Super[s + 1] - c0, nsrow = p->h_Lsip[s + 1] - p->h_Lsip[s];
-                double* panel = p->d_Lsx + p->h_Lsxp[s];
-                for (int64_t j0 = 0; j0 < nscol; j0 += sf::UPD_B) {
-                    const int b = (int)std::min<int64_t>(sf::UPD_B, nscol - j0);
-                    sf::launch_updown_diag(panel + j0 * nsrow + j0, nsrow, b, kw, sign, W, c0 + j0, rot, info, st);
-                    const int64_t below = nsrow - (j0 + b);
-                    sf::launch_updown_rows(panel + j0 * nsrow + j0 + b, nsrow, b, below, p->d_Lsi + p->h_Lsip[s] + j0 + b, kw, sign, W, rot, st);
-                    launches += below > 0 ? 2 : 1;
-                }
-            }
-            HIP_TRY(hipGetLastError());
-            p->upd_w_dirty = false;
+    const SfUpdownBlock B = sf_updown_parts(p);
+    int64_t launches = 0;
+    for (int64_t s : supers) {
+        const int64_t c0 = p->h_Super[s], nscol = p->h_Super[s + 1] - c0, nsrow = p->h_Lsip[s + 1] - p->h_Lsip[s];
+        double* panel = p->d_Lsx + p->h_Lsxp[s];
+        for (int64_t j0 = 0; j0 < nscol; j0 += sf::UPD_B) {
+            const int b = (int)std::min<int64_t>(sf::UPD_B, nscol - j0);
+            sf::launch_updown_diag(panel + j0 * nsrow + j0, nsrow, b, kw, sign, B.W, c0 + j0, B.rot, B.info, st);
+            const int64_t below = nsrow - (j0 + b);
+            sf::launch_updown_rows(panel + j0 * nsrow + j0 + b, nsrow, b, below, p->d_Lsi + p->h_Lsip[s] + j0 + b, kw, sign, B.W, B.rot, st);
+            launches += below > 0 ? 2 : 1;
         }
-        HIP_TRY(hipEventRecord(p->ev_s1, st));
-        HIP_TRY(hipMemcpyAsync(&h_info, info, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return SF_OK;
-    };
-    const int rrc = rotate();
+    }
+    return launches;
+}
+
+int sf_updown_collect(sf_chol_plan* p, int* h_info) {
+    hipStream_t st = p->stream;
+    HIP_TRY(hipEventRecord(p->ev_s1, st));
+    HIP_TRY(hipMemcpyAsync(h_info, sf_updown_parts(p).info, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return SF_OK;
+}
+
+int sf_updown_commit(sf_chol_plan* p, int rrc, int h_info, const std::vector<int64_t>& supers, int64_t launches) {
+    int64_t path_cols = 0;
+    for (int64_t s : supers) path_cols += p->h_Super[s + 1] - p->h_Super[s];
     float ms = 0;
     if (rrc == SF_OK && elapsed_ms(&ms, p->ev_s0, p->ev_s1)) p->last_updown_ms = ms;
     p->upd_path_supers = (int64_t)supers.size();
@@ -297,6 +277,66 @@ int update_run(sf_chol_plan* p, int sign, sf_long k, const sf_long* Wp, const sf
     }
     p->ok_gen = p->factor_gen;      // as for an import: the updated factor counts as factorized
     return SF_OK;
+}
+
+namespace {
+
+int update_run(sf_chol_plan* p, int sign, sf_long k, const sf_long* Wp, const sf_long* Wi, const sf_float* Wx, bool wx_dev, int flags) {
+    if (!p || (sign != SF_UPDATE && sign != SF_DOWNDATE) || k < 0 || !Wp) return SF_ERR_ARG;
+    if (int rc = sf_updown_accepts(p, flags)) return rc;
+    std::vector<int32_t> iperm;
+    if (flags & SF_DEV_PERM_IN)
+        if (int rc = sf_updown_inverse_ordering(p, iperm)) return rc;
+    std::vector<int64_t> supers;
+    std::vector<int32_t> rows;
+    int64_t bad = -1;
+    const int prc = sf::updown_path(sf_updown_struct(p), k, Wp, Wi, iperm.empty() ? nullptr : iperm.data(), supers, &bad, &rows);
+    if (prc == sf::UPDOWN_INADMISSIBLE) p->upd_bad_column = bad;      // (the stat that names it; nothing else of the plan changes)
+    if (prc != sf::UPDOWN_OK) return SF_ERR_ARG;
+    const int64_t nz = Wp[k] - Wp[0];
+    if (nz > 0 && !Wx) return SF_ERR_ARG;
+    if (wx_dev && nz > 0 && !sf_device_ptr_ok(p, Wx + Wp[0], (size_t)nz)) return SF_ERR_ARG;
+    if (k == 0) return SF_OK;
+    if (int rc = sf_updown_block(p)) return rc;
+
+    hipStream_t st = p->stream;
+    const SfUpdownBlock B = sf_updown_parts(p);
+    // where every value goes in the block of its chunk, and the values themselves
+    std::vector<int64_t> dest((size_t)std::max<int64_t>(nz, 1));
+    for (sf_long t = 0; t < k; ++t)
+        for (sf_long q = Wp[t]; q < Wp[t + 1]; ++q) dest[(size_t)(q - Wp[0])] = (int64_t)rows[(size_t)(q - Wp[0])] * sf::UPD_W + t % sf::UPD_W;
+    sf::DevMem<int64_t> d_dest;
+    sf::DevMem<double> d_val;
+    if (int rc = d_dest.alloc(dest.size())) return rc;
+    HIP_TRY(hipMemcpyAsync(d_dest, dest.data(), dest.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    const double* val = Wx ? Wx + Wp[0] : nullptr;
+    if (!wx_dev && nz > 0) {
+        if (int rc = d_val.alloc((size_t)nz)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_val, val, (size_t)nz * sizeof(double), hipMemcpyHostToDevice, st));
+        val = d_val;
+    }
+    HIP_TRY(hipMemsetAsync(B.info, 0, sizeof(double), st));
+
+    int64_t launches = 0;
+    int h_info = 0;
+    // From the first launch on the factor may be partly rotated: whatever goes wrong in here, the plan no longer holds a factor.
+    auto rotate = [&]() -> int {
+        HIP_TRY(hipEventRecord(p->ev_s0, st));
+        for (sf_long t0 = 0; t0 < k; t0 += sf::UPD_W) {
+            const int cw = (int)std::min<sf_long>(sf::UPD_W, k - t0), kw = kernel_width(cw);
+            // A finished chunk leaves the block zero again: the diagonal launches zero the rows of their columns, and every row a
+            // row launch writes is a column of an ancestor on the path.  Only a fresh block, or one an error left behind, is cleared.
+            if (int rc = sf_updown_clear_w(p)) return rc;
+            sf::launch_updown_scatter(d_dest + (Wp[t0] - Wp[0]), val + (Wp[t0] - Wp[0]), Wp[t0 + cw] - Wp[t0], B.W, st);
+            // (a chunk only touches the chains of its own columns, but a supernode off them sees zero rows of W: identities)
+            launches += sf_updown_rotate(p, supers, sign, kw);
+            HIP_TRY(hipGetLastError());
+            p->upd_w_dirty = false;
+        }
+        return sf_updown_collect(p, &h_info);
+    };
+    const int rrc = rotate();
+    return sf_updown_commit(p, rrc, h_info, supers, launches);
 }
 
 }  // namespace
@@ -320,11 +360,11 @@ int sf_chol_plan_update_path(const sf_chol_plan* p, sf_long k, const sf_long* Wp
     std::vector<int32_t> iperm;
     if (flags & SF_DEV_PERM_IN) {
         if (p->dry || !p->d_perm) return SF_ERR_ARG;
-        if (int rc = inverse_ordering(p, iperm)) return rc;
+        if (int rc = sf_updown_inverse_ordering(p, iperm)) return rc;
     }
     std::vector<int64_t> path;
     int64_t bad = -1;
-    const int prc = sf::updown_path(updown_struct(p), k, Wp, Wi, iperm.empty() ? nullptr : iperm.data(), path, &bad);
+    const int prc = sf::updown_path(sf_updown_struct(p), k, Wp, Wi, iperm.empty() ? nullptr : iperm.data(), path, &bad);
     if (bad_column) *bad_column = bad;
     if (prc != sf::UPDOWN_OK) return SF_ERR_ARG;
     *count = (sf_long)path.size();
