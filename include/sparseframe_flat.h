@@ -178,6 +178,39 @@ int sf_chol_plan_selinv_trace_device(sf_chol_plan *plan, sf_long m, const sf_flo
  * written.  The pairs go up in chunks of 65536 (stat "selinv_entries_chunk"). */
 int sf_chol_plan_selinv_entries(sf_chol_plan *plan, sf_long count, const sf_long *rows, const sf_long *cols, sf_float *out,
                                 sf_long *outside /* or NULL */);
+/* ---- adjoints on the pattern: what a solve, a quadratic form or a log-determinant contributes to the gradient with
+ * respect to the matrix values, as an array in set_values order.  M(V) is the matrix sf_chol_plan_set_values(V) assembles, as for
+ * sf_chol_plan_selinv_trace.  Plans: those sf_chol_plan_solve_device accepts (schedule-only, partial, sharded, mapped and out-of-core
+ * plans: SF_ERR_ARG).  SF_ERR_ARG -- a NULL pointer, k < 0, a short leading dimension, an unknown flag bit, a flag whose stored
+ * ordering or map is missing, a device pointer that sf_chol_plan_solve_device would refuse, an output that overlaps an input --
+ * leaves every output untouched.  Device state (the column and the kind of every position, 5 bytes each; for SF_ADJ_MAPPED the
+ * unmapped result and the map by source entry) is allocated by the first call that needs it and kept until destroy: stat
+ * "bytes_adjoint", not in "bytes_device".  "last_adjoint_ms": device time of the last call's kernels, copies excluded. ---- */
+#define SF_ADJ_MAPPED 4      /* out has nsrc doubles in the caller's own value layout, written through the map of sf_chol_plan_set_value_map */
+/* out such that  sum_p out[p] dV[p] = alpha sum_{c<k} y_c^T M(dV) x_c  for every dV: for position p of column j with row i = Li[p]
+ *     i != j:  out[p] = alpha sum_c (Y[i,c] X[j,c] + Y[j,c] X[i,c])          i == j:  out[p] = alpha sum_c Y[i,c] X[i,c]
+ * and exactly 0 where the assembly does not read the position (an entry given again later in its column).  With X = A^{-1} B,
+ * Y = A^{-1} G and alpha = -1 this is the gradient of a loss with respect to the values when G is its gradient with respect to X.
+ * Y, X: column-major n x k, ldy, ldx >= max(n, 1), permuted space; NULL only with k == 0.  k is limited by memory alone; k == 0
+ * writes zeros.  Needs the plan's structure only: no values, no factor -- it works before the first factorization and after a failed
+ * one.  Every out[p] is one accumulator over ascending c, one fma per product, (i, j) before (j, i), then one multiplication by alpha;
+ * no floating-point atomics: the same inputs give the same bits on every call, and a NaN in row r of Y or X reaches only the
+ * positions whose row or column is r.
+ * SF_ADJ_MAPPED: out has nsrc doubles, out[s] = the sum of the unmapped results of the positions p with map[p] == s, added to +0.0
+ * in ascending p (a map may name one source entry at several positions -- a symmetric source feeding both triangles of an LU plan,
+ * for one: they are summed, in this fixed order); a source entry no position names gets 0.  A plan without a stored map is refused.
+ * _device: Y, X, out in device memory of the plan's device; flags may add SF_DEV_PERM_IN: Y and X are in the caller's numbering and
+ * row perm[i] is read where row i is due (needs sf_chol_plan_set_ordering) -- bit for bit the result of the call on the permuted blocks. */
+int sf_chol_plan_adjoint_values(sf_chol_plan *plan, sf_long k, const sf_float *Y, sf_long ldy, const sf_float *X, sf_long ldx, double alpha,
+                                int flags /* 0 | SF_ADJ_MAPPED */, sf_float *out /* nnz; mapped: nsrc */);
+int sf_chol_plan_adjoint_values_device(sf_chol_plan *plan, int flags /* 0 | SF_DEV_PERM_IN | SF_ADJ_MAPPED */, sf_long k, const sf_float *dY,
+                                       sf_long ldy, const sf_float *dX, sf_long ldx, double alpha, sf_float *d_out);
+/* out such that  sum_p out[p] dV[p] = alpha sf_chol_plan_selinv_trace(dV)  for every dV -- alpha times the gradient of log det A with
+ * respect to the values: (i != j ? 2 : 1) alpha Sigma(i, j) where the assembly reads the position, exactly 0 where it does not
+ * (sf_chol_plan_selinv_values has neither the factor 2 nor the zeros).  Needs a valid arena exactly as sf_chol_plan_selinv_values
+ * does and is refused the same way.  flags: 0 or SF_ADJ_MAPPED (as above). */
+int sf_chol_plan_logdet_grad_values(sf_chol_plan *plan, double alpha, int flags, sf_float *out /* nnz; mapped: nsrc */);
+int sf_chol_plan_logdet_grad_values_device(sf_chol_plan *plan, double alpha, int flags, sf_float *d_out);
 /* SparseFrame_validate on the device (C:3141-3266; LU plans: L:3702-3858): b_i = 1 + i/n, solve with the resident factor,
  * r = A x - b from the plan's copy of the matrix values, *residual = |r|_inf / (|A|_1 |x|_inf + |b|_inf).  x_host may be NULL.
  * *residual is NaN when any r_i or x_i is not finite (NaN fails every `<=`); the return code is SF_OK all the same.  The struct
@@ -260,7 +293,8 @@ int sf_chol_plan_sample(sf_chol_plan *plan, sf_long nsamples, uint64_t seed, uin
  * (or managed) memory of the plan's device, or whose allocation ends before the block does, is SF_ERR_ARG. ---- */
 /* the ordering for SF_DEV_PERM_IN / SF_DEV_PERM_OUT and sf_chol_plan_permute_device: perm[new] = old, n entries, as
  * sf_symbolic_create takes it (NULL: the identity).  Not a permutation of 0..n-1: SF_ERR_ARG, the plan keeps what it had.  Uploaded
- * as 32-bit indices, like the plan's own row lists; stat "bytes_ordering" (with the value map's bytes, not in "bytes_device").
+ * as 32-bit indices, like the plan's own row lists; stat "bytes_ordering" (with the value map's bytes, not in "bytes_device"),
+ * stat "ordering_set" (1 once a call has succeeded).
  * Cholesky and LU plans. */
 int sf_chol_plan_set_ordering(sf_chol_plan *plan, const sf_long *perm);
 #define SF_OP_SOLVE   0   /* X <- A^{-1} B                                   (Cholesky and LU plans) */
@@ -710,6 +744,23 @@ int sf_lu_plan_selinv_trace_device(sf_lu_plan *plan, sf_long m, const sf_float *
 /* out[k] = Sigma(rows[k], cols[k]) with (i, j) taken literally; outside the pattern of L + U: a quiet NaN, counted */
 int sf_lu_plan_selinv_entries(sf_lu_plan *plan, sf_long count, const sf_long *rows, const sf_long *cols, sf_float *out,
                               sf_long *outside /* or NULL */);
+/* sf_chol_plan_adjoint_values for an LU plan: sum_p outL[p] dVL[p] + sum_p outU[p] dVU[p] = alpha sum_c y_c^T M(dVL, dVU) x_c.
+ *     outL[p] = alpha sum_c Y[i,c] X[j,c]       for position p at (i, j) of the L structure (column j, i = Li[p])
+ *     outU[p] = alpha sum_c Y[j,c] X[Ui[p],c]   for position p of row j of U
+ * and exactly 0 where the assembly does not read the position: a superseded duplicate, and the diagonal positions of L (the diagonal
+ * is U's).  U aliasing L: outL carries both sums, the diagonal once, and outU must be NULL.  SF_ADJ_MAPPED: outL has nsrc doubles
+ * for both parts of the stored map (L's positions are added before U's), outU must be NULL.  For X = A^{-1} B the matching Y is
+ * A^{-T} G (SF_OP_TRANS); for X = A^{-T} B the gradient is the call with the two blocks exchanged. */
+int sf_lu_plan_adjoint_values(sf_lu_plan *plan, sf_long k, const sf_float *Y, sf_long ldy, const sf_float *X, sf_long ldx, double alpha,
+                              int flags /* 0 | SF_ADJ_MAPPED */, sf_float *outL, sf_float *outU /* or NULL */);
+int sf_lu_plan_adjoint_values_device(sf_lu_plan *plan, int flags /* 0 | SF_DEV_PERM_IN | SF_ADJ_MAPPED */, sf_long k, const sf_float *dY,
+                                     sf_long ldy, const sf_float *dX, sf_long ldx, double alpha, sf_float *d_outL, sf_float *d_outU);
+/* sum_p outL[p] dVL[p] + sum_p outU[p] dVU[p] = alpha sf_lu_plan_selinv_trace(dVL, dVU): alpha times the gradient of log|det A|.
+ * outL[p] = alpha Sigma(j, i), outU[p] = alpha Sigma(Ui[p], j) where the assembly reads the position, 0 elsewhere -- the diagonal
+ * once, from U; U aliasing L: outL[p] = alpha (Sigma(j, i) + Sigma(i, j)) off the diagonal.  Arena and refusals as
+ * sf_lu_plan_selinv_values; outU, SF_ADJ_MAPPED as above. */
+int sf_lu_plan_logdet_grad_values(sf_lu_plan *plan, double alpha, int flags, sf_float *outL, sf_float *outU /* or NULL */);
+int sf_lu_plan_logdet_grad_values_device(sf_lu_plan *plan, double alpha, int flags, sf_float *d_outL, sf_float *d_outU);
 double sf_lu_plan_stat(const sf_lu_plan *plan, const char *name);
 int sf_lu_plan_set_profiling(sf_lu_plan *plan, int on);
 int sf_lu_plan_destroy(sf_lu_plan *plan);

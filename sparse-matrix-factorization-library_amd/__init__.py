@@ -15,3 +15,12 @@ from .api import (  # noqa: F401
 )
 from . import gen  # noqa: F401
 from .sharded import ShardedCholesky, ShardedFactorization  # noqa: F401
+
+
+def __getattr__(name):
+    """`autograd` and `Factorization` (torch.autograd for plans) on first use: importing the package needs no torch"""
+    if name in ("autograd", "Factorization"):
+        import importlib
+        mod = importlib.import_module(".autograd", __name__)
+        return mod if name == "autograd" else mod.Factorization
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

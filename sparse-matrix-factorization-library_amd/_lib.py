@@ -326,6 +326,21 @@ for _n in ("sf_chol_plan_selinv_values", "sf_chol_plan_selinv_values_device", "s
            "sf_lu_plan_selinv_values_t", "sf_lu_plan_selinv_values_t_device", "sf_chol_plan_selinv_trace", "sf_chol_plan_selinv_trace_device",
            "sf_lu_plan_selinv_trace", "sf_lu_plan_selinv_trace_device", "sf_chol_plan_selinv_entries", "sf_lu_plan_selinv_entries"):
     getattr(lib, _n).restype = C.c_int
+# adjoints on the pattern (sf_adjoint.hip); device addresses travel as integers
+lib.sf_chol_plan_adjoint_values.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64, C.c_double, C.c_int, c_double_p]
+lib.sf_chol_plan_adjoint_values_device.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double,
+                                                   C.c_void_p]
+lib.sf_lu_plan_adjoint_values.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64, C.c_double, C.c_int, c_double_p,
+                                          c_double_p]
+lib.sf_lu_plan_adjoint_values_device.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double,
+                                                 C.c_void_p, C.c_void_p]
+lib.sf_chol_plan_logdet_grad_values.argtypes = [C.c_void_p, C.c_double, C.c_int, c_double_p]
+lib.sf_chol_plan_logdet_grad_values_device.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p]
+lib.sf_lu_plan_logdet_grad_values.argtypes = [C.c_void_p, C.c_double, C.c_int, c_double_p, c_double_p]
+lib.sf_lu_plan_logdet_grad_values_device.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
+for _n in ("adjoint_values", "adjoint_values_device", "logdet_grad_values", "logdet_grad_values_device"):
+    getattr(lib, "sf_chol_plan_" + _n).restype = C.c_int
+    getattr(lib, "sf_lu_plan_" + _n).restype = C.c_int
 lib.sf_lu_plan_stat.argtypes = [C.c_void_p, C.c_char_p]
 lib.sf_lu_plan_stat.restype = C.c_double
 lib.sf_lu_plan_set_profiling.argtypes = [C.c_void_p, C.c_int]

@@ -839,8 +839,118 @@ class _SelinvPatternMixin:
         return self.selinv_trace(dA, dAU)
 
 
+ADJ_MAPPED = 4      # SF_ADJ_MAPPED
+
+
+def _host_block(B, rows, what):
+    """a host block of columns: 1-D (rows,) or 2-D (rows, k), any memory order -> (float64 array with unit stride along the rows,
+    k, leading dimension).  A float64 block with unit stride along the rows (a column-major array or a row slice of one) is
+    passed as it is, with its own leading dimension; anything else is copied."""
+    B = np.asarray(B)
+    if B.ndim not in (1, 2) or B.shape[0] != rows:
+        raise ValueError(f"{what}: expected shape ({rows},) or ({rows}, k), got {B.shape}")
+    ldmin = max(rows, 1)
+    if B.ndim == 1:
+        return _f64(B), 1, ldmin
+    k = B.shape[1]
+    direct = B.dtype == np.float64 and (rows <= 1 or B.strides[0] == 8) and (k <= 1 or (B.strides[1] % 8 == 0 and B.strides[1] >= 8 * ldmin))
+    if not direct:
+        B = np.asfortranarray(B, dtype=np.float64)
+    return B, k, (ldmin if k <= 1 else B.strides[1] // 8)
+
+
+class _AdjointMixin:
+    """the gradient of solves, quadratic forms and log-determinants with respect to the matrix values, as arrays in set_values
+    order or (mapped) in the caller's own value layout (sf_*_plan_adjoint_values / _logdet_grad_values).  Permuted
+    space unless perm_in says otherwise.  The autograd module builds on the device forms."""
+
+    def _adj_fn(self, what):
+        return getattr(lib, ("sf_lu_plan_" if isinstance(self, LUPlan) else "sf_chol_plan_") + what)
+
+    def _adj_counts(self, mapped, what):
+        """(entries of the first output, entries of the second or None)"""
+        if mapped:
+            if getattr(self, "_nsrc", None) is None:
+                raise ValueError(f"{what}: mapped=True needs a value map (set_value_map)")
+            return self._nsrc, None
+        own_u = isinstance(self, LUPlan) and not self._alias
+        return self._nnz, (self._unz if own_u else None)
+
+    def _adj_host(self, what, head, alpha, mapped):
+        nl, nu = self._adj_counts(mapped, what)
+        out = np.zeros(max(nl, 1), dtype=np.float64)
+        outU = np.zeros(max(nu, 1), dtype=np.float64) if nu is not None else None
+        args = head + [float(alpha), ADJ_MAPPED if mapped else 0, _dp(out)]
+        if isinstance(self, LUPlan):
+            args.append(_dp(outU) if outU is not None else None)
+        fn = self._adj_fn(what)
+        check(fn(self._h, *args), fn.__name__)
+        return (out[:nl], outU[:nu]) if outU is not None else out[:nl]
+
+    def _adj_dev_outs(self, what, out, outU, mapped):
+        nl, nu = self._adj_counts(mapped, what)
+        if (outU is not None) and nu is None:
+            raise ValueError(f"{what}: outU is for an LUPlan with its own U structure (unmapped)")
+        torch = self._dev_sync()
+        dev = f"cuda:{self.device}"
+        if out is None:
+            out = torch.empty(nl, dtype=torch.float64, device=dev)
+        if outU is None and nu is not None:
+            outU = torch.empty(nu, dtype=torch.float64, device=dev)
+        L, _, _, one = _dev_tensor(out, nl, self.device, what + " (out)", writable=True)
+        ptrs = [L.data_ptr() or None]
+        if nu is not None:
+            U, _, _, oneu = _dev_tensor(outU, nu, self.device, what + " (outU)", writable=True)
+            one = one and oneu
+            ptrs.append(U.data_ptr() or None)
+        elif isinstance(self, LUPlan):
+            ptrs.append(None)
+        if not one:
+            raise ValueError(f"{what}: the outputs must be 1-D")
+        return out, outU, ptrs
+
+    def adjoint_values(self, Y, X, alpha=1.0, mapped=False):
+        """out with sum(out * dV) = alpha * sum_c y_c^T M(dV) x_c for every dV, M(dV) the matrix set_values(dV) assembles: Y, X
+        (n,) or (n, k) host arrays.  CholPlan -> (nnz,); LUPlan -> (outL, outU), or outL alone when U aliases L; mapped -> (nsrc,)
+        in the caller's own value layout.  Positions the assembly ignores get 0.  Needs no factor."""
+        what = "adjoint_values"
+        Yb, k, ldy = _host_block(Y, self.n, what + " (Y)")
+        Xb, kx, ldx = _host_block(X, self.n, what + " (X)")
+        if kx != k:
+            raise ValueError(f"{what}: Y and X must have as many columns, got {k} and {kx}")
+        return self._adj_host(what, [k, _dp(Yb), ldy, _dp(Xb), ldx], alpha, mapped)
+
+    def adjoint_values_device(self, Y, X, out=None, outU=None, alpha=1.0, perm_in=False, mapped=False):
+        """adjoint_values on device tensors ((n,) or column-major (n, k)); perm_in: Y and X are in the caller's numbering
+        (set_ordering).  out / outU: 1-D float64 on the device, allocated when None.  Returns out, or (out, outU)."""
+        what = "adjoint_values_device"
+        Yt, k, ldy, _ = _dev_tensor(Y, self.n, self.device, what + " (Y)")
+        Xt, kx, ldx, _ = _dev_tensor(X, self.n, self.device, what + " (X)")
+        if kx != k:
+            raise ValueError(f"{what}: Y and X must have as many columns, got {k} and {kx}")
+        out, outU, ptrs = self._adj_dev_outs(what, out, outU, mapped)
+        fn = self._adj_fn(what)
+        flags = (1 if perm_in else 0) | (ADJ_MAPPED if mapped else 0)
+        check(fn(self._h, flags, k, Yt.data_ptr() or None, ldy, Xt.data_ptr() or None, ldx, float(alpha), *ptrs), fn.__name__)
+        return (out, outU) if outU is not None else out
+
+    def logdet_grad_values(self, alpha=1.0, mapped=False):
+        """alpha times the gradient of logdet() with respect to the values, after selinv(): the Sigma of every position the
+        assembly reads -- twice off the diagonal of a CholPlan, the transposed entry for an LUPlan -- and 0 at the others.
+        Shapes as adjoint_values.  logdet_grad(dA) == sum(logdet_grad_values() * dA) up to rounding."""
+        return self._adj_host("logdet_grad_values", [], alpha, mapped)
+
+    def logdet_grad_values_device(self, out=None, outU=None, alpha=1.0, mapped=False):
+        """logdet_grad_values into device tensors"""
+        what = "logdet_grad_values_device"
+        out, outU, ptrs = self._adj_dev_outs(what, out, outU, mapped)
+        fn = self._adj_fn(what)
+        check(fn(self._h, float(alpha), ADJ_MAPPED if mapped else 0, *ptrs), fn.__name__)
+        return (out, outU) if outU is not None else out
+
+
 class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin, _DeviceIOMixin, _SelinvPatternMixin,
-               _UpdatePathMixin):
+               _AdjointMixin, _UpdatePathMixin):
     """Device-resident supernodal Cholesky (flat ABI).  Raises if no HIP device is present.
     phase/load_top: multi-GPU sharding (sf_chol_plan_create_sharded); default = the whole matrix on one device.
     rank/nranks (with phase): distributed top (sf_chol_plan_create_distributed), run with factorize_phase(0) and then
@@ -1140,7 +1250,8 @@ class CholPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, 
         self.close()
 
 
-class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin, _DeviceIOMixin, _SelinvPatternMixin):
+class LUPlan(_ShardedPlanMixin, _ValidateMixin, _ScheduleMixin, _RefineMixin, _CondestMixin, _DeviceIOMixin, _SelinvPatternMixin,
+             _AdjointMixin):
     """Device-resident supernodal no-pivot LU (flat ABI, sf_lu_plan_*).  `sym` comes from analyze(..., method='lu').
     phase/load_top/rank/nranks: distributed multi-GPU plan (sf_lu_plan_create_distributed), as CholPlan."""
 

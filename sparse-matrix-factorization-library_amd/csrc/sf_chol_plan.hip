@@ -772,6 +772,7 @@ double sf_chol_plan_stat(const sf_chol_plan* p, const char* name) {
     if (k == "last_quadform_ms") return p->last_quadform_ms;
     if (k == "last_sample_ms") return p->last_sample_ms;
     if (k == "bytes_ordering") return (double)p->bytes_ordering;
+    if (k == "ordering_set") return p->d_perm ? 1.0 : 0.0;
     if (k == "bytes_gram") return (double)p->bytes_gram;
     if (k == "last_gram_ms") return p->last_gram_ms;
     if (k == "last_gram_parts") return (double)p->last_gram_parts;
@@ -786,6 +787,10 @@ double sf_chol_plan_stat(const sf_chol_plan* p, const char* name) {
     if (k == "selinv_pattern_tile") return sf_selpat_constant(1);
     if (k == "selinv_entries_chunk") return sf_selpat_constant(2);
     if (k == "selinv_pattern_max_m") return sf_selpat_constant(3);
+    if (k == "factor_generation") return (double)p->factor_gen;
+    if (k == "factor_usable") return (p->ok_gen >= 0 && p->ok_gen >= p->fact_gen && !p->upd_failed) ? 1.0 : 0.0;
+    if (k == "bytes_adjoint") return (double)p->bytes_adjoint;
+    if (k == "last_adjoint_ms") return p->last_adjoint_ms;
     if (k == "last_refine_iters") return (double)p->last_refine_iters;
     if (k == "last_refine_berr0") return p->last_refine_berr0;
     if (k == "last_refine_berr") return p->last_refine_berr;

@@ -352,6 +352,7 @@ int sf_chol_plan_set_value_map(sf_chol_plan* p, sf_long nsrc, const sf_long* map
         p->bytes_ordering += (nl + nu) * sizeof(int64_t);
     }
     p->vmap_nsrc = nsrc;
+    ++p->vmap_gen;      // (what sf_adjoint.hip derived from the old map is stale)
     return SF_OK;
 }
 int sf_lu_plan_set_value_map(sf_lu_plan* p, sf_long nsrc, const sf_long* mapL, const sf_long* mapU) {

@@ -200,6 +200,32 @@ void launch_lu_selinv_diag(int64_t n, const double* SL, const SelStruct& t, doub
 // buf: ceil(n / 256) partial sums, then sum log|U_jj| and the parity of the negative U_jj (as a double); neg: ceil(n / 256) counts
 void launch_lu_logdet(int64_t n, const double* PU, const SelStruct& t, double* buf, int32_t* neg, hipStream_t st);
 
+// ---- adjoints on the pattern of A (sf_adjoint.hip, sf_*_plan_adjoint_values / _logdet_grad_values) ----
+// The marks of a position p at (row i, column j) of a structure: which of the two products its output collects.
+constexpr uint8_t ADJ_A = 1;                            // Y[i, c] X[j, c]: the assembly puts V[p] at M(i, j)
+constexpr uint8_t ADJ_B = 2;                            // Y[j, c] X[i, c]: ... at M(j, i)
+// how launch_adj_index marks a position from the load maps (map < 0: the assembly does not read the position)
+enum AdjSide {
+    ADJ_SIDE_CHOL = 0,      // live: A, and B too off the diagonal
+    ADJ_SIDE_LU_L = 1,      // live in mapA: A
+    ADJ_SIDE_LU_ALIAS = 2,  // live in mapA (L's map): A; live in mapB (U's map over the same structure): B, on the diagonal A
+    ADJ_SIDE_LU_U = 3,      // (ptr, idx) = U by rows; live in mapA: B
+};
+// one launch each, thread = position, 256 threads per workgroup; count <= 0: nothing launched
+// col[p] = the column (U: row) j with ptr[j] <= p < ptr[j + 1], mark[p] as AdjSide says; p < count = ptr[n]
+void launch_adj_index(const int64_t* ptr, const int32_t* idx, int32_t n, int64_t count, int side, const int64_t* mapA, const int64_t* mapB,
+                      int32_t* col, uint8_t* mark, hipStream_t st);
+// out[p] = alpha * sum_{c < k} ([A] Y[r(i), c] X[r(j), c] + [B] Y[r(j), c] X[r(i), c]), i = idx[p], j = col[p], r = perm or the identity
+// (perm null); ascending c, one fma per product, A before B; mark[p] == 0 or k == 0: +0.0.  Y, X column-major.
+void launch_adj_values(const int32_t* idx, const int32_t* col, const uint8_t* mark, int64_t count, const int32_t* perm, int k, const double* Y,
+                       int64_t ldy, const double* X, int64_t ldx, double alpha, double* out, hipStream_t st);
+// out[p] = alpha * ((mapA[p] >= 0 ? w S[mapA[p] + shiftA] : nothing) + (mapB && mapB[p] >= 0 ? S[mapB[p] + shiftB] : nothing)), w = 2
+// where mark[p] has both ADJ_A and ADJ_B and twice is set, else 1; neither live: +0.0
+void launch_adj_logdet(const int64_t* mapA, int64_t shiftA, const int64_t* mapB, int64_t shiftB, const uint8_t* mark, int twice, int64_t count,
+                       const double* S, double alpha, double* out, hipStream_t st);
+// out[s] = 0.0 + tmp[list[sptr[s]]] + ... + tmp[list[sptr[s + 1] - 1]] in that order, s < nsrc
+void launch_adj_scatter(const int64_t* sptr, const int64_t* list, int64_t nsrc, const double* tmp, double* out, hipStream_t st);
+
 // ---- Sigma on the pattern of A (sf_selinv_pattern.hip, sf_*_plan_selinv_values / _trace / _entries) ----
 constexpr int SELPAT_CHUNK = 8;                         // columns of V a lane keeps partial sums for at a time (registers, no scratch)
 constexpr int SELPAT_EPT = 8;                           // entries per lane: that many independent map -> Sigma gathers in flight

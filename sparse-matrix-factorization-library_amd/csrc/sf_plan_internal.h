@@ -288,6 +288,17 @@ struct sf_chol_plan : sf_plan_handles, SfSchedule {
     size_t bytes_selinv_pattern = 0;
     double last_selinv_pattern_ms = 0;
     int64_t last_selinv_outside = 0;
+    // sf_*_plan_adjoint_values / _logdet_grad_values (sf_adjoint.hip): the column and the term marks of every position (L's,
+    // then U's of an LU plan with its own U structure), the unmapped result of a mapped or host-array call, and the value map by source
+    // entry (adj_vmap_gen: vmap_gen it was built from) -- each allocated by the first call that needs it (bytes_adjoint, not in
+    // bytes_device)
+    sf::DevMem<int32_t> d_adj_col;
+    sf::DevMem<uint8_t> d_adj_mark;
+    sf::DevMem<double> d_adj_tmp;
+    sf::DevMem<int64_t> d_adj_src;              // sptr[nsrc + 1] | the positions by source entry, ascending within one
+    int64_t vmap_gen = 0, adj_vmap_gen = -1, adj_src_entries = 0;
+    size_t bytes_adjoint = 0;
+    double last_adjoint_ms = 0;
     // sf_chol_plan_residual / sf_chol_plan_refine (sf_refine.hip): A by rows as positions into d_Lx / d_Ux (unsymmetric LU: also by
     // columns, for |A|_1), the vectors b | x | best x | r | w and the scalars; one set of allocations made by the first call
     // (not in bytes_device).  rf_anorm_gen = factor_gen the stored |A|_1 belongs to.
