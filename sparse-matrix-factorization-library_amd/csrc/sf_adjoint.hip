@@ -288,7 +288,7 @@ int adj_entry(sf_chol_plan* p, bool lu, bool dev, int flags, sf_long k, const do
     }
     if ((!outL && count_l > 0) || (need_u && !outU && count_u > 0) || (!need_u && outU)) return SF_ERR_ARG;
     if (!adj_accepts(p, lu) || (mapped && !p->d_vmap) || (perm && !p->d_perm)) return SF_ERR_ARG;
-    if (logdet && (!p->d_sel || p->sel_gen != p->factor_gen)) return SF_ERR_ARG;
+    if (logdet && (!p->d_sel || !p->fs.selinv_matches())) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     if (count_l + count_u <= 0) return SF_OK;
     AdjJob j{logdet ? -1 : (int)k, perm ? p->d_perm.get() : nullptr, Y, X, ldy, ldx, alpha};

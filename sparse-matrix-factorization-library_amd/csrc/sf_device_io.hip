@@ -222,8 +222,7 @@ int dio_values_done(sf_chol_plan* p) {
     } else {
         HIP_TRY(hipStreamSynchronize(st));
     }
-    p->values_set = true;
-    ++p->factor_gen;        // the resident factor (and a selected inverse from it) no longer belongs to the values
+    p->fs.values_changed();
     return SF_OK;
 }
 

@@ -91,7 +91,7 @@ struct SolverSlot {
 // per-rank plans of a multi-handler factorization (parts), see sf_handlers_solve_resident
 struct Resident {
     sf_chol_plan* plan = nullptr;
-    int epoch = 0;
+    int plan_epoch = 0;                 // the factorization of `plan` the host copy belongs to
     std::vector<sf_chol_plan*> parts;
     std::vector<int> part_epochs;
     std::shared_ptr<SolverSlot> slot;
@@ -319,7 +319,7 @@ static int factorize_all_handlers(struct common_info_struct* common, struct gpu_
         // handler's device (sf_handlers_solve_resident)
         Resident R;
         R.parts = entry->plans;
-        for (sf_chol_plan* q : entry->plans) R.part_epochs.push_back(q->epoch);
+        for (sf_chol_plan* q : entry->plans) R.part_epochs.push_back(q->fs.factor_epoch());
         R.slot = entry->slot;
         R.comms = M.comms;
         R.device = list[0].gpuIndex_physical;
@@ -577,7 +577,7 @@ int sf_handlers_factorize(struct common_info_struct* common, struct gpu_info_str
     if (!rc && plan->ooc_groups <= 1) {        // (an out-of-core factor exists on the host only: its solves take the host sweep)
         Resident R;
         R.plan = plan;
-        R.epoch = plan->epoch;
+        R.plan_epoch = plan->fs.factor_epoch();
         std::lock_guard<std::mutex> g(g_res_mu);
         g_resident[(const void*)Lsx_out] = std::move(R);
     } else if (!rc) {
@@ -619,7 +619,7 @@ int sf_handlers_solve_resident_sym(const sf_float* Lsx_host, const sf_float* b, 
         // device to device, the solve then runs there.  Needs the symbolic arrays (to build that plan) and room for the whole
         // factor on one device; otherwise the caller solves on the host.
         for (size_t r = 0; r < R.parts.size(); ++r)
-            if (R.parts[r]->epoch != R.part_epochs[r]) { g_resident.erase(it); return why("a rank's plan holds a later factorization"); }
+            if (R.parts[r]->fs.factor_epoch() != R.part_epochs[r]) { g_resident.erase(it); return why("a rank's plan holds a later factorization"); }
         SolverSlot& S = *R.slot;
         // The factor stays where it is and the ranks solve together (sf_chol_plan_solve_distributed), one host thread per rank as in
         // the factorization.  SF_SOLVE=gather: gather the panels into a whole plan on the first handler's device instead (below).
@@ -677,7 +677,7 @@ int sf_handlers_solve_resident_sym(const sf_float* Lsx_host, const sf_float* b, 
             S.imported = R.part_epochs;
         }
         plan = S.plan;
-    } else if (plan->epoch != R.epoch || plan->partial) {
+    } else if (plan->fs.factor_epoch() != R.plan_epoch || plan->partial) {
         g_resident.erase(it);
         return why("the plan holds a later factorization");
     }

@@ -9,7 +9,7 @@
 //                           rehearsals on a one-GPU box): event hand-shakes + a sum kernel on that device.  Same call sites
 //                           and ordering as the RCCL kind; never used when the ranks have devices of their own.
 //   sf_chol_plan_factorize_distributed   phase 0 (own subtrees), then per segment: pack -> all-reduce(sum) -> chain +
-//                           this rank's share of the split GEMMs (sf_chol_plan.hip), all enqueued on the plan's stream with
+//                           this rank's share of the split GEMMs (sf_segments.hip), all enqueued on the plan's stream with
 //                           no host synchronisation; optionally with the overlapped copy-back of this rank's pieces.
 //
 // The reference has no inter-GPU path: its device handlers exchange panels through pinned host memory under one task

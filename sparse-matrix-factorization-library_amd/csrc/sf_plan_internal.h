@@ -11,6 +11,7 @@
 
 #include "sf_device_mem.h"
 #include "sf_download.h"
+#include "sf_factor_state.h"
 #include "sf_kernels.h"
 #include "sf_schedule.h"
 #include "sf_updown_path.h"
@@ -63,12 +64,15 @@ void sf_solve_sweep_bwd(sf_chol_plan* p, double* x, int width, bool transpose_di
 void sf_solve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, hipStream_t st);
 // the end of a solve: read the info word, synchronize; SF_ERR_HIP if a bounded in-launch wait ran out
 int sf_solve_finish(sf_chol_plan* p, hipStream_t st);
-// ---- shared with the condition estimate and the transposed solves (sf_refine.hip) ----
+// ---- the factor's state (sf_factor_state.h) behind the one call that may wait for the device (sf_factorize.hip) ----
 // the last factorization that was started has succeeded (a finished but unsynchronised one is collected here); an imported factor
 // counts.  NOT required: that it is a factorization of the current values.
 bool sf_factor_usable(sf_chol_plan* p);
+// ... and it is the factor of the current values (a finished but unsynchronised factorization of them is collected here)
+bool sf_factor_current(sf_chol_plan* p);
+// ---- shared with the condition estimate and the transposed solves (sf_refine.hip) ----
 // *d_anorm = device address of |A|_1 of the plan's CURRENT values, up to date on `st` (the residual's row / column form is set up by
-// the first call, the norm recomputed when factor_gen has moved); the plans sf_chol_plan_residual accepts
+// the first call, the norm recomputed when the values have changed); the plans sf_chol_plan_residual accepts
 int sf_refine_anorm(sf_chol_plan* p, const double** d_anorm, hipStream_t st);
 // ---- shared with the device-pointer solves (sf_device_io.hip) ----
 // x <- A^{-T} x for an LU plan (sf_solve_t.hip; the caller has zeroed the sync block on the stream)
@@ -97,8 +101,8 @@ int sf_updown_clear_w(sf_chol_plan* p);
 int64_t sf_updown_rotate(sf_chol_plan* p, const std::vector<int64_t>& supers, int sign, int kw);
 // record ev_s1, read the info word, wait for the stream
 int sf_updown_collect(sf_chol_plan* p, int* h_info);
-// the state protocol after the factor was written (rrc: what the launches and sf_updown_collect returned): the stats, hash_epoch,
-// factor_gen, fact_done, ok_gen; a failure (rrc or h_info) leaves upd_failed.  Returns the call's status.
+// after the factor was written (rrc: what the launches and sf_updown_collect returned): the stats and the state's factor_replaced;
+// a failure (rrc or h_info) leaves the factor broken.  Returns the call's status.
 int sf_updown_commit(sf_chol_plan* p, int rrc, int h_info, const std::vector<int64_t>& supers, int64_t launches);
 // ---- the host protocol of every entry point that takes columns through the resident factor (sf_apply.hip) ----
 // the plan is whole and resident: one rank's, in core, with the solve's task lists
@@ -160,7 +164,7 @@ struct SfDownload : sf::DlSchedule {             // the schedule and the knobs (
     sf::DevMem<sf::FillTile> d_fill;            // the LU direct download's sf::FillTile[], grouped by download event (fill_first)
     // ---- a running download ----
     sf::DlGate gate;                            // where the enqueue thread and the copy workers meet (sf_download.h)
-    bool active = false;                        // run_launches records the events and publishes them
+    bool active = false;                        // sf_run_launches records the events and publishes them
     size_t next_ev = 0;                         // enqueue thread only: the first event not yet recorded
     double* host = nullptr;                     // destination (reference layout)
     std::vector<std::thread> threads;
@@ -257,11 +261,8 @@ struct sf_chol_plan : sf_plan_handles, SfSchedule {
     int64_t vmap_nsrc = 0;
     sf::DevMem<double> d_dio_part;
     size_t bytes_ordering = 0;
-    // sf_chol_plan_selinv (sf_selinv.hip).  Generations of the factor: factor_gen moves whenever the values or the resident factor
-    // change (set_values, the start of a factorization, an import); fact_gen = factor_gen of the last factorization started,
-    // ok_gen = that of the last one that succeeded (sf_chol_plan_sync) or of an import; sel_gen = factor_gen the arena was computed from
-    int64_t factor_gen = 0, fact_gen = -1, ok_gen = -1, sel_gen = -1;
-    bool fact_done = false;         // the last factorization started has had all its launches enqueued
+    SfFactorState fs;               // values, factor, selected inverse, fingerprints: which belongs to which (sf_factor_state.h)
+    // sf_chol_plan_selinv (sf_selinv.hip)
     struct SelBig { sf::SelUnit u; int zslabs, sslabs; };
     struct SelStep { int64_t small_first, small_count, big_first, big_count; };   // one level: big units, then narrow supernodes
     bool sel_scheduled = false;
@@ -301,22 +302,20 @@ struct sf_chol_plan : sf_plan_handles, SfSchedule {
     double last_adjoint_ms = 0;
     // sf_chol_plan_residual / sf_chol_plan_refine (sf_refine.hip): A by rows as positions into d_Lx / d_Ux (unsymmetric LU: also by
     // columns, for |A|_1), the vectors b | x | best x | r | w and the scalars; one set of allocations made by the first call
-    // (not in bytes_device).  rf_anorm_gen = factor_gen the stored |A|_1 belongs to.
+    // (not in bytes_device)
     sf::DevMem<int64_t> d_rf_ptr, d_rf_pos, d_rf_cptr, d_rf_cpos;
     sf::DevMem<int32_t> d_rf_col, d_rf_ccol;
     sf::DevMem<double> d_rf_vec;
-    int64_t rf_entries = 0, rf_anorm_gen = -1;
+    int64_t rf_entries = 0;
     size_t bytes_refine = 0;
     int last_refine_iters = 0;
     double last_refine_berr0 = 0, last_refine_berr = 0, last_refine_ms = 0, last_residual_ms = 0;
     // sf_*_plan_condest (sf_solve_t.hip): x | the sign vector | the iteration's scalars, allocated by the first call (not in
     // bytes_device)
     // sf_chol_plan_update (sf_updown.hip): the row-major n x UPD_W block of W, the rotation pairs of one 64-column block
-    // and the info word, one allocation made by the first call (bytes_update, not in bytes_device).  upd_failed: a downdate left
-    // the factor half rotated -- it counts as not factorized until the next factorization starts or a factor is imported.
+    // and the info word, one allocation made by the first call (bytes_update, not in bytes_device)
     sf::DevMem<double> d_upd;
     size_t bytes_update = 0;
-    bool upd_failed = false;
     bool upd_w_dirty = true;        // the block of W may hold something: zero it before the next chunk (a finished chunk leaves zeros)
     double last_updown_ms = 0;
     int64_t upd_path_supers = 0, upd_path_cols = 0, upd_launches = 0, upd_bad_column = -1;
@@ -344,11 +343,9 @@ struct sf_chol_plan : sf_plan_handles, SfSchedule {
     sf::DevMem<PotrfTask> d_potrf;
     sf::DevMem<TrsmTask> d_trsm;
     sf::DevMem<StepTask> d_steps;
-    sf::DevMem<int> d_flags;     // k_step: one flag per (panel, fused step); == epoch once its diagonal block is factored
+    sf::DevMem<int> d_flags;     // k_step: one flag per (panel, fused step); == the factorization's epoch once its diagonal block is factored
     sf::DevMem<double> d_tinv;   // k_step: inverses of the 16 x 16 diagonal sub-blocks, per diagonal task of the running launch
-    int epoch = 0;
-    std::vector<uint64_t> h_hash;    // per-supernode fingerprints of the factor of epoch hash_epoch (sf_plan_panel_hashes)
-    int hash_epoch = -1;
+    std::vector<uint64_t> h_hash;    // per-supernode fingerprints of the factor (sf_plan_panel_hashes; fs.hashes_current())
     sf::DevMem<GemmProb> d_probs;
     sf::DevMem<GemmTask> d_gtasks;
     sf::DevMem<GemmTask> d_stasks;   // tiles of k_update_small
@@ -356,13 +353,9 @@ struct sf_chol_plan : sf_plan_handles, SfSchedule {
     sf::DevMem<int32_t> d_relmap;
 
     size_t bytes_device = 0;
-    bool values_set = false;
-
     bool profiling = false;
     double last_ms = 0, last_load_ms = 0, last_panel_ms = 0, last_update_ms = 0;
     double last_kind_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int last_status = SF_OK;
-
 };
 
 template <class Body, class Tail>
@@ -390,11 +383,23 @@ int sf_apply_chunks(sf_chol_plan* p, const SfApply& a, SfStretch& t, Body&& body
     return sf_apply_chunks(p, a, t, body, [](double*, sf_long, int) { return SF_OK; });
 }
 
+// The factorization driver (sf_factorize.hip): launches [l0, l1) of the plan on its stream; first: the start of a factorization
+// (timer, memsets, assembly); last: its end (timer, and with sync the status)
+int sf_run_launches(sf_chol_plan* p, size_t l0, size_t l1, bool first, bool last, int sync);
+// This rank's window [lo, hi) of a launch's `total` divisible items (GEMM launches: stream-K units; k_update_small: tiles); all of
+// them unless the launch is split over a group.  The boundaries are the same doubles on the two ranks they separate, so the windows
+// of a group's members tile [0, total) exactly (checked for every launch of 256^3 / 8 by tests/test_config4_schedules.py).
+static inline void launch_window(const Launch& L, int64_t total, int64_t* lo, int64_t* hi) {
+    *lo = 0; *hi = total;
+    if (!L.split) return;
+    *lo = (int64_t)((double)total * L.share_lo);
+    *hi = L.share_hi >= 1.0 ? total : (int64_t)((double)total * L.share_hi);
+}
 // Overlapped download (sf_download.hip).  sf_dl_begin starts the copy workers of a factorization whose launches are
-// about to be enqueued with run_launches (which records and publishes the piece events while dl.active is set);
+// about to be enqueued with sf_run_launches (which records and publishes the piece events while dl.active is set);
 // sf_dl_end publishes what is left, waits for the workers and returns SF_OK or the first error.
 int sf_dl_begin(sf_chol_plan* p, double* host_out);
-// run_launches' two calls: record the events of everything that is final once `done` launches have been enqueued and tell the
+// sf_run_launches' two calls: record the events of everything that is final once `done` launches have been enqueued and tell the
 // copy workers; out of core, before group g takes over its buffer: wait until the pieces of the groups that held it (and, top mode
 // 2, the top panels whose places it takes) have left the device -- SF_ERR_HIP when the download was aborted meanwhile
 hipError_t sf_dl_publish(sf_chol_plan* p, size_t done);
@@ -405,9 +410,9 @@ double sf_selpat_constant(int which);
 // rank does not store.  Computed once per factorization (about one read of the factor), then cached.
 extern "C" int sf_plan_panel_hashes(sf_chol_plan* p, const uint64_t** out);
 int sf_dl_end(sf_chol_plan* p);
-// gathers the panels of the parts (plans of several ranks, one pattern) into the whole plan dst (sf_chol_plan.hip)
+// gathers the panels of the parts (plans of several ranks, one pattern) into the whole plan dst (sf_segments.hip)
 int sf_plan_import_from(sf_chol_plan* dst, sf_chol_plan* const* parts, int nparts);
-// pipelined segment sums (sf_chol_plan.hip), used by sf_chol_plan_factorize_distributed
+// pipelined segment sums (sf_segments.hip), used by sf_chol_plan_factorize_distributed
 int sf_seg_begin(sf_chol_plan* p, sf_long k, void** dptr, sf_long* count);
 void* sf_plan_stream2(sf_chol_plan* p);
 int sf_seg_reduced(sf_chol_plan* p, sf_long k);

@@ -232,7 +232,7 @@ int refine_setup(sf_chol_plan* p) {
     p->d_rf_vec = std::move(vec);
     p->rf_entries = (int64_t)nr;
     p->bytes_refine = bytes;
-    p->rf_anorm_gen = -1;
+    p->fs.anorm_forgotten();
     return SF_OK;
 }
 
@@ -251,12 +251,12 @@ sf::RefineForm row_form(const sf_chol_plan* p) {
 // v.s[5] = |A|_1 of the current values: the column sums of |A| (unsymmetric LU: the column form; symmetric: the row form serves),
 // recomputed when the values have changed
 int refine_anorm(sf_chol_plan* p, const RefineVecs& v, hipStream_t st) {
-    if (p->rf_anorm_gen == p->factor_gen) return SF_OK;
+    if (p->fs.anorm_current()) return SF_OK;
     const bool unsym = p->lu && !p->u_alias;
     HIP_TRY(hipMemsetAsync(v.s + 5, 0, sizeof(double), st));
     sf::launch_refine_abs_sums(unsym ? sf::RefineForm{p->d_rf_cptr, p->d_rf_ccol, p->d_rf_cpos, p->d_Lx, p->d_Ux} : row_form(p), p->n,
                                v.s + 5, st);
-    p->rf_anorm_gen = p->factor_gen;
+    p->fs.anorm_computed();
     return SF_OK;
 }
 
@@ -293,13 +293,8 @@ int refine_read(sf_chol_plan* p, const RefineVecs& v, RefineScalars* out, hipStr
 
 }  // namespace
 
-bool sf_factor_usable(sf_chol_plan* p) {
-    if (p->fact_done && p->ok_gen < p->fact_gen) (void)sf_chol_plan_sync(p);
-    return p->ok_gen >= 0 && p->ok_gen >= p->fact_gen;
-}
-
 int sf_refine_anorm(sf_chol_plan* p, const double** d_anorm, hipStream_t st) {
-    if (refine_refused(p) || !p->values_set) return SF_ERR_ARG;
+    if (refine_refused(p) || !p->fs.has_values()) return SF_ERR_ARG;
     if (int rc = refine_setup(p)) return rc;
     const RefineVecs v = refine_vecs(p);
     if (int rc = refine_anorm(p, v, st)) return rc;
@@ -312,7 +307,7 @@ extern "C" {
 
 int sf_chol_plan_residual(sf_chol_plan* p, const sf_float* b_host, const sf_float* x_host, sf_float* r_host, sf_float* berr, sf_float* nerr) {
     if (!p || !b_host || !x_host) return SF_ERR_ARG;
-    if (refine_refused(p) || !p->values_set) return SF_ERR_ARG;
+    if (refine_refused(p) || !p->fs.has_values()) return SF_ERR_ARG;
     if (berr) *berr = 0.0;
     if (nerr) *nerr = 0.0;
     if (p->n <= 0) return SF_OK;
@@ -351,7 +346,7 @@ int sf_chol_plan_residual_weights(sf_chol_plan* p, sf_float* w_host) {
 
 int sf_chol_plan_refine(sf_chol_plan* p, const sf_float* b_host, sf_float* x_host, int max_iter, double tol, sf_float* berr_out) {
     if (!p || !b_host || !x_host || max_iter < 0) return SF_ERR_ARG;
-    if (refine_refused(p) || !p->values_set || (p->nsuper > 0 && !p->d_solve)) return SF_ERR_ARG;
+    if (refine_refused(p) || !p->fs.has_values() || (p->nsuper > 0 && !p->d_solve)) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     if (!sf_factor_usable(p)) return SF_ERR_ARG;
     if (berr_out) *berr_out = 0.0;

@@ -257,11 +257,6 @@ double unit_flops(double m, double w) { return 2.0 * m * m * w + 2.0 * m * w * w
 
 }  // namespace
 
-bool sf_selinv_factor_current(sf_chol_plan* p) {
-    if (p->ok_gen != p->factor_gen && p->fact_gen == p->factor_gen) (void)sf_chol_plan_sync(p);
-    return p->ok_gen == p->factor_gen;
-}
-
 int sf_selinv_schedule(sf_chol_plan* p) {
     const int64_t ns = p->nsuper;
     const std::vector<int64_t>& Lsip = p->h_Lsip;
@@ -388,7 +383,7 @@ int sf_chol_plan_selinv(sf_chol_plan* p) {
 
 int sf_chol_plan_get_selinv_range(sf_chol_plan* p, sf_long e_begin, sf_long e_end, sf_float* out) {
     if (!p || p->lu || !sf_plan_whole_resident(p) || e_begin < 0 || e_end > p->xsize || e_end < e_begin || (!out && e_end > e_begin)) return SF_ERR_ARG;
-    if (!p->d_sel || p->sel_gen != p->factor_gen) return SF_ERR_ARG;
+    if (!p->d_sel || !p->fs.selinv_matches()) return SF_ERR_ARG;
     if (e_end == e_begin) return SF_OK;
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipMemcpyAsync(out, p->d_sel + e_begin, (e_end - e_begin) * sizeof(double), hipMemcpyDeviceToHost, p->stream));
@@ -403,7 +398,7 @@ int sf_chol_plan_selinv_diag(sf_chol_plan* p, sf_float* d) {
 
 int sf_chol_plan_logdet(sf_chol_plan* p, sf_float* out) {
     if (!p || !out || p->lu || !sf_plan_whole_resident(p)) return SF_ERR_ARG;
-    if (!sf_selinv_factor_current(p)) return SF_ERR_ARG;
+    if (!sf_factor_current(p)) return SF_ERR_ARG;
     *out = 0.0;
     if (p->n <= 0) return SF_OK;
     HIP_TRY(hipSetDevice(p->device));

@@ -158,7 +158,6 @@ static inline SelStruct sel_struct(const sf_chol_plan* p) {
 
 // ---- host side, defined in sf_selinv.hip ----
 // a successful factorization of the plan's current values is on the device (a finished but unsynchronised one is collected here)
-bool sf_selinv_factor_current(sf_chol_plan* p);
 // the schedule (first call): units, pair table, scratch sizes, flops_selinv (an LU unit costs twice a Cholesky one)
 int sf_selinv_schedule(sf_chol_plan* p);
 
@@ -188,13 +187,13 @@ static inline int sf_selinv_alloc(sf_chol_plan* p, size_t arena, size_t scratch)
 // scratch(): doubles of scratch, asked once the schedule is known.
 template <class Scratch, class Big, class Small>
 int sf_selinv_run(sf_chol_plan* p, size_t arena, Scratch&& scratch, Big&& big, Small&& small) {
-    if (!sf_selinv_factor_current(p)) return SF_ERR_ARG;
+    if (!sf_factor_current(p)) return SF_ERR_ARG;
     if (p->n <= 0) return SF_OK;
     HIP_TRY(hipSetDevice(p->device));
     if (!p->sel_scheduled)
         if (int rc = sf_selinv_schedule(p)) return rc;
     if (int rc = sf_selinv_alloc(p, arena, scratch())) return rc;
-    p->sel_gen = -1;
+    p->fs.selinv_started();
     hipStream_t st = p->stream;
     HIP_TRY(hipEventRecord(p->ev_s0, st));
     for (const auto& s : p->sel_steps) {
@@ -206,7 +205,7 @@ int sf_selinv_run(sf_chol_plan* p, size_t arena, Scratch&& scratch, Big&& big, S
     HIP_TRY(hipStreamSynchronize(st));
     float ms = 0;
     if (elapsed_ms(&ms, p->ev_s0, p->ev_s1)) p->last_selinv_ms = ms;
-    p->sel_gen = p->factor_gen;
+    p->fs.selinv_finished();
     return SF_OK;
 }
 
@@ -214,7 +213,7 @@ int sf_selinv_run(sf_chol_plan* p, size_t arena, Scratch&& scratch, Big&& big, S
 static inline int sf_selinv_diag_run(sf_chol_plan* p, sf_float* d,
                                      void (*launch)(int64_t, const double*, const sf::SelStruct&, double*, hipStream_t)) {
     if (p->n <= 0) return SF_OK;
-    if (!p->d_sel || p->sel_gen != p->factor_gen) return SF_ERR_ARG;
+    if (!p->d_sel || !p->fs.selinv_matches()) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     launch((int64_t)p->n, p->d_sel, sf::sel_struct(p), p->d_sel_diag, p->stream);
     HIP_TRY(hipGetLastError());

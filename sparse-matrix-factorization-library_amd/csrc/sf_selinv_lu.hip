@@ -390,7 +390,7 @@ int sf_lu_plan_selinv(sf_lu_plan* p) {
 
 int sf_lu_plan_get_selinv_range(sf_lu_plan* p, sf_long e_begin, sf_long e_end, sf_float* out) {
     if (!p || !p->lu || !sf_plan_whole_resident(p) || e_begin < 0 || e_end > p->xsize || e_end < e_begin || (!out && e_end > e_begin)) return SF_ERR_ARG;
-    if (!p->d_sel || p->sel_gen != p->factor_gen) return SF_ERR_ARG;
+    if (!p->d_sel || !p->fs.selinv_matches()) return SF_ERR_ARG;
     if (e_end == e_begin) return SF_OK;
     HIP_TRY(hipSetDevice(p->device));
     const int64_t count = e_end - e_begin;
@@ -411,7 +411,7 @@ int sf_lu_plan_selinv_diag(sf_lu_plan* p, sf_float* d) {
 
 int sf_lu_plan_logdet(sf_lu_plan* p, sf_float* logabs, int* sign) {
     if (!p || !logabs || !p->lu || !sf_plan_whole_resident(p)) return SF_ERR_ARG;
-    if (!sf_selinv_factor_current(p)) return SF_ERR_ARG;
+    if (!sf_factor_current(p)) return SF_ERR_ARG;
     *logabs = 0.0;
     if (sign) *sign = 1;
     if (p->n <= 0) return SF_OK;

@@ -227,7 +227,7 @@ namespace {
 // the plans every entry point here accepts: of the right kind, whole and resident, with an arena that belongs to the resident factor
 bool selpat_ready(const sf_chol_plan* p, bool lu) {
     if (!p || p->lu != lu || !sf_plan_whole_resident(p)) return false;
-    if (!p->d_sel || p->sel_gen != p->factor_gen) return false;
+    if (!p->d_sel || !p->fs.selinv_matches()) return false;
     return p->d_loadmapL && (!lu || p->d_loadmapU);
 }
 

@@ -767,7 +767,7 @@ int sf_chol_plan_solve(sf_chol_plan* p, const sf_float* b_host, sf_float* x_host
     if (!p || !b_host || !x_host) return SF_ERR_ARG;
     if (p->partial || (p->nsuper > 0 && !p->d_solve)) return SF_ERR_ARG;
     if (p->dry) return SF_ERR_ARG;        // a schedule-only plan has no device side
-    if (p->upd_failed) return SF_ERR_ARG;       // a failed downdate: no factor until the next factorization
+    if (p->fs.broken()) return SF_ERR_ARG;       // a failed downdate: no factor until the next factorization
     HIP_TRY(hipSetDevice(p->device));
     if (p->n <= 0) return SF_OK;
     const SfCols src{const_cast<double*>(b_host), p->n, false, nullptr}, dst{x_host, p->n, false, nullptr};
@@ -789,7 +789,7 @@ int sf_chol_plan_solve_many(sf_chol_plan* p, sf_long nrhs, const sf_float* B, sf
     if (!p || !B || !X || nrhs < 0) return SF_ERR_ARG;
     // (not sf_plan_whole_resident: this entry point has never looked at nranks)
     if (p->dry || p->partial || p->ooc_groups > 1 || (p->nsuper > 0 && !p->d_solve)) return SF_ERR_ARG;
-    if (p->upd_failed) return SF_ERR_ARG;
+    if (p->fs.broken()) return SF_ERR_ARG;
     const sf_long ldmin = std::max<sf_long>(p->n, 1);
     if (ldb < ldmin || ldx < ldmin) return SF_ERR_ARG;
     if ((const void*)X == (const void*)B && ldx != ldb) return SF_ERR_ARG;

@@ -483,7 +483,7 @@ void tsolve_sweeps(sf_chol_plan* p, double* x, int width, bool transpose_diag, h
 namespace {
 
 int condest(sf_chol_plan* p, sf_float* anorm, sf_float* ainv_norm_est) {
-    if (!sf_plan_whole_resident(p) || !p->values_set) return SF_ERR_ARG;
+    if (!sf_plan_whole_resident(p) || !p->fs.has_values()) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     if (!sf_factor_usable(p)) return SF_ERR_ARG;
     *anorm = 0.0;

@@ -204,7 +204,7 @@ int sf_updown_accepts(sf_chol_plan* p, int flags) {
     if (!sf_plan_whole_resident(p)) return SF_ERR_ARG;
     if ((flags & SF_DEV_PERM_IN) && !p->d_perm) return SF_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
-    if (p->upd_failed || !sf_factor_usable(p)) return SF_ERR_ARG;
+    if (p->fs.broken() || !sf_factor_usable(p)) return SF_ERR_ARG;
     return SF_OK;
 }
 
@@ -266,17 +266,11 @@ int sf_updown_commit(sf_chol_plan* p, int rrc, int h_info, const std::vector<int
     p->upd_path_supers = (int64_t)supers.size();
     p->upd_path_cols = path_cols;
     p->upd_launches = launches;
-    p->hash_epoch = -1;             // the factor changed without a factorization: cached fingerprints are stale
-    ++p->factor_gen;                // ... and so is a selected inverse
-    p->fact_done = false;           // nothing left for sf_chol_plan_sync to collect: it must not move ok_gen back to fact_gen
-    if (rrc != SF_OK || h_info) {
-        p->upd_failed = true;       // half rotated: no factor until the next factorization
-        p->upd_w_dirty = true;
-        p->ok_gen = -1;
-        return rrc != SF_OK ? rrc : SF_ERR_NOT_POSDEF;
-    }
-    p->ok_gen = p->factor_gen;      // as for an import: the updated factor counts as factorized
-    return SF_OK;
+    const bool ok = rrc == SF_OK && !h_info;
+    p->fs.factor_replaced(ok);      // as for an import: the updated factor counts as factorized; half rotated: no factor
+    if (ok) return SF_OK;
+    p->upd_w_dirty = true;
+    return rrc != SF_OK ? rrc : SF_ERR_NOT_POSDEF;
 }
 
 namespace {
