@@ -622,6 +622,31 @@ def test_struct_entry_point_reuses_cached_plan(oracle):
     common.close()
 
 
+def test_struct_entry_point_evicts_the_oldest_plan():
+    """a handler caches two plans: a third pattern evicts the one used longest ago, a repeated pattern touches its entry, and a
+    matrix whose plan was evicted is no longer resident -- its solve takes the host sweep and is still right"""
+    common = sf.CommonInfo(dev_slot_size=1 << 30)
+    mis = {}
+    for g in (10, 11, 12):
+        n, Cp, Ci, Cx = gen.laplacian_lower(g, g)
+        mi = mis[g] = sf.MatrixInfo()
+        mi.set_csc(n, Cp, Ci, Cx)
+        mi.analyze(common)
+        mi.factorize(common)
+        assert mi.validate() <= TOL_RESIDUAL
+    assert common.plan_builds() == 3
+    mis[12].factorize(common)
+    assert common.plan_builds() == 3            # cached, and now the newer of the two
+    mis[10].factorize(common)
+    assert common.plan_builds() == 4            # the oldest, evicted by 12 x 12: built again, in the place of 11 x 11
+    solves = sf.lib.sf_handlers_resident_solves()
+    assert mis[11].validate() <= TOL_RESIDUAL   # its Lsx of the first round; the plan is gone
+    assert sf.lib.sf_handlers_resident_solves() == solves
+    for mi in mis.values():
+        mi.cleanup()
+    common.close()
+
+
 def test_gemm_register_staged_form(oracle, monkeypatch):
     """k_gemm stages its operand tiles by LDS-DMA (global_load_lds_dwordx4) by default; SF_GEMM_DMA=0 selects the
     register-staged form.  Both must give the oracle's factor (wide supernodes: K tails, odd panel offsets, edge tiles)."""
